@@ -5,9 +5,17 @@ and compiled population resident in HBM; per-step host work: launch, per-tree di
 decisions, 1024 losses back to the host).  `value` counts the node-rows the device actually
 evaluated (srhip_last_work: a failed tree's skipped rows are not counted).  Steps are issued as
 the search issues populations: step k + 1 submitted (srhip_eval_loss_submit) before step k is
-waited for; --sync times blocking srhip_eval_loss calls instead (both forms are in the line).
+waited for; --sync times blocking srhip_eval_loss calls instead (--full puts both forms in the line).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cpu-seconds S] [--mode islands|rowshard]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--cpu-seconds S] [--mode islands|rowshard]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the
+bench measures, each in runs of its own after the timed steps: the other step form, the grid launch,
+no early exit, the undecided-tree count, end-to-end and pipelined fresh populations, the CPU
+baseline (c4: the gradient launch alone and its CPU baseline; c1 / c3: the CPU search).
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (finite
+numbers only: a failed tree's +Inf loss is a 0 there and a 1 in DIR/<name>_nonfinite.npy).
 
 N > 1 (launched by torch.distributed.run), --mode islands (default): each rank evaluates its own
 population on its own GPU (islands, src/SymbolicRegression.jl:746-793) and every step's results
@@ -33,6 +41,39 @@ PEAK_FP32_TFLOPS = 157.3  # MI355X FP32 vector (= FP32 MFMA) peak, MI355X_MICROA
 PEAK_FP64_TFLOPS = 78.6   # MI355X FP64 vector peak
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` (name -> what the timed path returned in its last step) as
+    dirname/<name>.npy, float64 arrays as they are and everything else (flags, counts) as float32.
+    Every file holds finite numbers only, so that two builds' dumps can be subtracted: the path returns
+    +Inf as the loss of a tree whose evaluation failed (the reference's contract), so a floating-point
+    output is written as <name>.npy with 0 at its non-finite entries, plus <name>_nonfinite.npy with
+    each entry's class (0 finite, 1 +Inf, 2 -Inf, 3 NaN).  Together the two files hold the output
+    exactly."""
+    import numpy as np
+
+    files = {}
+
+    def save(name, a):
+        if a.size > 1 << 20:  # a fixed, seeded sample of a large output (the whole dump stays small)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, 1 << 20, replace=False))]
+        files[name + ".npy"] = a
+
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        floating = a.dtype.kind == "f"
+        a = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+        if floating:  # (both files of a sampled output hold the same elements: the seed and the size agree)
+            cls = np.select([np.isposinf(a), np.isneginf(a), np.isnan(a)], [1, 2, 3], 0).astype(np.float32)
+            save(name + "_nonfinite", cls)
+            a = np.where(cls == 0, a, 0).astype(a.dtype)
+        save(name, a)
+    total = sum(a.nbytes for a in files.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"  # (checked before anything is written)
+    os.makedirs(dirname, exist_ok=True)
+    for fname, a in files.items():
+        np.save(os.path.join(dirname, fname), a)
+
+
 class _Done:
     """A synchronous evaluation's result in the shape of an EvalTicket (the timed loops take either)."""
 
@@ -52,17 +93,26 @@ def parse(argv=None):
     ap.add_argument("--launch-check", action="store_true",
                     help="(tests) every rank prints its rank / world / device assignment as JSON and exits before "
                          "touching the GPU")
-    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: c2 20, c4 10)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default: c2 20, c4 10; c1 / c3: search iterations, default 2 / 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure (other step forms and launch forms, "
+                         "fresh-population pipeline, per-kernel roofline runs, CPU baselines); off: the line "
+                         "carries only what the timed steps themselves measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32, or float64 where the path computes in it); rank 0 writes")
     ap.add_argument("--warmup", type=int, default=None,
                     help="untimed steps first (default: c2 30 -- the GPU reaches its steady clocks over the "
                          "first ~50 ms of work -- c4 3)")
     ap.add_argument("--ntrees", type=int, default=1024)
     ap.add_argument("--rows", type=int, default=1_000_000)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="--full: target CPU-baseline sample duration")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--headline-only", action="store_true",
-                    help="c2: skip the extra lines (derived columns, no early exit) -- profiler runs, whose "
-                         "per-kernel average must be the headline kernel's alone")
+                    help="c2 --full without the other launch forms (grid launch, no early exit) and the "
+                         "fresh-population pipeline")
     ap.add_argument("--binops", default="+,-,*,/", help="(tuning) binary operators of the C2 population")
     ap.add_argument("--unaops", default="cos,exp", help="(tuning) unary operators of the C2 population")
     ap.add_argument("--mode", default="islands", choices=("islands", "rowshard"),
@@ -79,13 +129,16 @@ def parse(argv=None):
                     help="c2 (default, the headline metric); c4: batched constant optimisation; c1 / c3: "
                          "equation_search (README example / 10M x 10 islands over the ranks)")
     ap.add_argument("--iterations", type=int, default=0,
-                    help="c1/c3: search iterations (default: c1 2 of the config's 40, c3 1)")
+                    help="c1/c3: search iterations (default: --steps when given, else c1 2 of the config's "
+                         "40, c3 1)")
     ap.add_argument("--ncycles", type=int, default=0, help="c1/c3: ncycles_per_iteration (default 550)")
     ap.add_argument("--parallelism", default="multithreading", choices=("multithreading", "multiprocessing"),
                     help="c1/c3: islands as threads of one process, or in worker processes (:multiprocessing)")
     ap.add_argument("--procs", type=int, default=0, help="c1/c3 multiprocessing: worker processes "
                     "(default min(populations per GPU, 16))")
     args = ap.parse_args(argv)
+    if args.config in ("c1", "c3") and not args.iterations and args.steps is not None:
+        args.iterations = args.steps  # the search's timed step is one iteration
     if args.steps is None:
         args.steps = 20 if args.config == "c2" else 10
     if args.warmup is None:
@@ -287,6 +340,8 @@ def main():
     nominal_value = work * world * args.steps / dt
     kern_ms = float(np.mean(kms))
     achieved = done_flops / (kern_ms * 1e-3) / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"losses": l, "did_succeed": ok})
 
     def timed_steps(pr, pipe=1):
         """(seconds for args.steps evaluations after the warmup, max over ranks; mean kernel ms;
@@ -316,51 +371,78 @@ def main():
         nr = float(np.mean([w["node_rows"] for w in wk]))
         return d, float(np.mean(km)), fl, nr
 
-    # the same population with derived columns forced on (the launch picks the plain program for C2:
-    # every node of every tree evaluated by its own instruction, over longer row blocks; DESIGN.md
-    # §3.1) -- reported beside it
-    # the other step form beside the headline's (synchronous calls vs the submit/wait pipeline)
-    dt_alt, kern_alt, _, nr_alt = timed_steps(prog, 1 if depth > 1 else 2)
-    step_forms = {
-        ("pipelined" if depth > 1 else "synchronous"): {"ms_per_step": ms_per_step, "kernel_ms": kern_ms,
-                                                        "value": value, "headline": True},
-        ("synchronous" if depth > 1 else "pipelined"): {"ms_per_step": dt_alt * 1e3 / args.steps,
-                                                        "kernel_ms": kern_alt,
-                                                        "value": nr_alt * world * args.steps / dt_alt,
-                                                        "headline": False},
-        "note": "synchronous: one blocking srhip_eval_loss per step; pipelined: step k + 1 submitted "
-                "(srhip_eval_loss_submit) before step k is waited for",
+    def more_c2():
+        """--full: (the line's further `extra` entries, cpu_baseline), each from runs of its own after
+        the timed steps."""
+        # the other step form beside the headline's (synchronous calls vs the submit/wait pipeline)
+        dt_alt, kern_alt, _, nr_alt = timed_steps(prog, 1 if depth > 1 else 2)
+        step_forms = {
+            ("pipelined" if depth > 1 else "synchronous"): {"ms_per_step": ms_per_step, "kernel_ms": kern_ms,
+                                                            "value": value, "headline": True},
+            ("synchronous" if depth > 1 else "pipelined"): {"ms_per_step": dt_alt * 1e3 / args.steps,
+                                                            "kernel_ms": kern_alt,
+                                                            "value": nr_alt * world * args.steps / dt_alt,
+                                                            "headline": False},
+            "note": "synchronous: one blocking srhip_eval_loss per step; pipelined: step k + 1 submitted "
+                    "(srhip_eval_loss_submit) before step k is waited for",
+        }
+        nan4 = (float("nan"),) * 4
+        dt_grid, kern_grid, fl_grid, nr_grid = nan4
+        dt_full, kern_full, fl_full, nr_full = nan4
+        # the same population through the round-2 grid launch (row blocks x tree groups, no probe)
+        if not args.headline_only:
+            os.environ["SRHIP_NO_PERSISTENT"] = "1"
+            dt_grid, kern_grid, fl_grid, nr_grid = timed_steps(prog)
+            del os.environ["SRHIP_NO_PERSISTENT"]
+        # ... and without the early exit of failed trees (every row of every tree evaluated)
+        if not args.headline_only:
+            os.environ["SRHIP_NO_EARLY_EXIT"] = "1"
+            dt_full, kern_full, fl_full, nr_full = timed_steps(prog)
+            del os.environ["SRHIP_NO_EARLY_EXIT"]
+
+        # trees whose did_succeed needs the precise pass (the bound max|v| x rows reaches half the overflow
+        # threshold): srhip_eval_loss runs it for them inside every step
+        psums, pchk = prog.eval_loss_partials(ds, loss)
+        undecided = int(np.sum(prog.finalize(nfeat, psums, pchk)[2] == 2))
+
+        # end-to-end per population (host compile of 1024 fresh trees + upload + eval)
+        t0 = time.perf_counter()
+        p2 = srhip.Program(ctx, nodes, offs, opts, np.float32)
+        p2.eval_loss(ds, loss)
+        e2e_ms = (time.perf_counter() - t0) * 1e3
+        p2.close()
+        pipeline = None if args.headline_only else population_pipeline(srhip, workloads, ctx, ds, loss, opts, rank, args)
+
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu:
+            cpu = cpu_baseline(nodes, offs, opts, X, y, args.cpu_seconds)
+        return {
+            "end_to_end_ms_per_population": e2e_ms,
+            "population_pipeline": pipeline,
+            "step_forms": step_forms,
+            "undecided_trees_per_step": undecided,
+            "grid_launch": {"value": nr_grid * world * args.steps / dt_grid, "kernel_ms": kern_grid,
+                            "frac": fl_grid / (kern_grid * 1e-3) / 1e12 / PEAK_FP32_TFLOPS,
+                            "nominal_value": work * world * args.steps / dt_grid,
+                            "note": "SRHIP_NO_PERSISTENT=1: the round-2 launch (row blocks x tree groups)"},
+            "no_early_exit": {"value": nr_full * world * args.steps / dt_full, "kernel_ms": kern_full,
+                              "frac": fl_full / (kern_full * 1e-3) / 1e12 / PEAK_FP32_TFLOPS,
+                              "note": "SRHIP_NO_EARLY_EXIT=1: failed trees evaluated on every row"},
+        }, cpu
+
+    # a plain run ends here: the line carries what the timed steps themselves measured.  --full: the
+    # bench's other measurements, each in runs of its own (more_c2)
+    extra = {
+        "compile_ms_1024_trees": compile_ms,
+        # population scoring rate: every live tree's nodes x every row per step / step time (the
+        # rows a failed tree skipped counted as if evaluated)
+        "nominal_value": nominal_value,
+        "evaluated_fraction": done_node_rows / (work * world * args.steps),
     }
-    nan4 = (float("nan"),) * 4
-    dt_grid, kern_grid, fl_grid, nr_grid = nan4
-    dt_full, kern_full, fl_full, nr_full = nan4
-    # the same population through the round-2 grid launch (row blocks x tree groups, no probe)
-    if not args.headline_only:
-        os.environ["SRHIP_NO_PERSISTENT"] = "1"
-        dt_grid, kern_grid, fl_grid, nr_grid = timed_steps(prog)
-        del os.environ["SRHIP_NO_PERSISTENT"]
-    # ... and without the early exit of failed trees (every row of every tree evaluated)
-    if not args.headline_only:
-        os.environ["SRHIP_NO_EARLY_EXIT"] = "1"
-        dt_full, kern_full, fl_full, nr_full = timed_steps(prog)
-        del os.environ["SRHIP_NO_EARLY_EXIT"]
-
-    # trees whose did_succeed needs the precise pass (the bound max|v| x rows reaches half the overflow
-    # threshold): srhip_eval_loss runs it for them inside every step
-    psums, pchk = prog.eval_loss_partials(ds, loss)
-    undecided = int(np.sum(prog.finalize(nfeat, psums, pchk)[2] == 2))
-
-    # end-to-end per population (host compile of 1024 fresh trees + upload + eval)
-    t0 = time.perf_counter()
-    p2 = srhip.Program(ctx, nodes, offs, opts, np.float32)
-    p2.eval_loss(ds, loss)
-    e2e_ms = (time.perf_counter() - t0) * 1e3
-    p2.close()
-    pipeline = None if args.headline_only else population_pipeline(srhip, workloads, ctx, ds, loss, opts, rank, args)
-
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
-        cpu = cpu_baseline(nodes, offs, opts, X, y, args.cpu_seconds)
+    if args.full:
+        more, cpu = more_c2()
+        extra.update(more)
 
     # the kernel variant the library picks for this launch (csrc/srhip_eval.hip pick_rows_per_lane)
     kst = 2 if st["max_stack"] <= 2 else (4 if st["max_stack"] <= 4 else 8)
@@ -420,23 +502,7 @@ def main():
                 "op_mix": op_mix(nodes, opts),
             },
             "cpu_baseline": cpu,
-            "extra": {
-                "compile_ms_1024_trees": compile_ms, "end_to_end_ms_per_population": e2e_ms,
-                "population_pipeline": pipeline,
-                "step_forms": step_forms,
-                "undecided_trees_per_step": undecided,
-                # population scoring rate: every live tree's nodes x every row per step / step time (the
-                # rows a failed tree skipped counted as if evaluated)
-                "nominal_value": nominal_value,
-                "evaluated_fraction": done_node_rows / (work * world * args.steps),
-                "grid_launch": {"value": nr_grid * world * args.steps / dt_grid, "kernel_ms": kern_grid,
-                                "frac": fl_grid / (kern_grid * 1e-3) / 1e12 / PEAK_FP32_TFLOPS,
-                                "nominal_value": work * world * args.steps / dt_grid,
-                                "note": "SRHIP_NO_PERSISTENT=1: the round-2 launch (row blocks x tree groups)"},
-                "no_early_exit": {"value": nr_full * world * args.steps / dt_full, "kernel_ms": kern_full,
-                                  "frac": fl_full / (kern_full * 1e-3) / 1e12 / PEAK_FP32_TFLOPS,
-                                  "note": "SRHIP_NO_EARLY_EXIT=1: failed trees evaluated on every row"},
-            },
+            "extra": extra,
         }
         print(json.dumps(out))
     if native is not None:
@@ -741,6 +807,8 @@ def bench_rowshard(args):
     tw = torch.tensor([done], dtype=torch.float64, device=red)
     dist.all_reduce(tw, op=dist.ReduceOp.SUM)
     dt, coll_max, kern_max = (float(v) for v in tt.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"losses": l, "did_succeed": ok})
     if rank == 0:
         print(json.dumps({
             "metric": "tree-node x row evals/sec (whole node), 1k trees x 10M rows f32 row-sharded over the ranks",
@@ -877,6 +945,36 @@ def bench_c4(args):
         out, improved, fcalls = step()
     ctx.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"losses": out, "improved": improved, "fcalls": fcalls,
+                                         "constants": np.concatenate(prog.get_constants())})
+    st = prog.stats()
+    fin = np.isfinite(base)
+    line = {
+        "metric": "C4 batched constant optimisation: wall time per optimize_constants over the population",
+        "value": dt * 1e3, "unit": "ms", "higher_is_better": False, "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt * 1e3, "dtype": "f64", "data": "synthetic (X ~ N(0,1) 5x100k; fixed-size-20 trees, >= 2 consts)",
+        "config": {"workload": f"C4: {ntrees} trees x {rows} rows Float64, BFGS(8) + 2 restarts",
+                   "ntrees": ntrees, "rows": rows, "nodes": int(st["total_nodes"])},
+        "objective_evals_per_s": float(np.sum(fcalls)) / dt,
+        "improved_trees": int(improved.sum()),
+        "mean_loss_before": float(np.mean(base[fin])), "mean_loss_after": float(np.mean(out[fin])),
+        # the mean is dominated by a few overflow-scale losses; the median shows the typical tree
+        "median_loss_before": float(np.median(base[fin])), "median_loss_after": float(np.median(out[fin])),
+        # a tree whose loss stays at ~1e250 fixes the arithmetic mean: the log-mean shows the whole population
+        "mean_log10_loss_before": float(np.mean(np.log10(np.maximum(base[fin], 1e-300)))),
+        "mean_log10_loss_after": float(np.mean(np.log10(np.maximum(out[fin], 1e-300)))),
+        "cpu_baseline": None,
+    }
+    if args.full:
+        line.update(more_c4(args, ctx, prog, ds, loss, nodes, offs, opts, X, y, rows))
+    print(json.dumps(line))
+
+
+def more_c4(args, ctx, prog, ds, loss, nodes, offs, opts, X, y, rows):
+    """--full: the gradient launch alone with its roofline entry, and the CPU baseline."""
+    import numpy as np
+
     # gradient launch alone (all 512 trees' loss + d loss / d c), HIP events around the dual-number
     # kernel on the library's stream
     st = prog.stats()
@@ -896,25 +994,11 @@ def bench_c4(args):
     opn = np.array([int(np.sum(nodes[offs[t]:offs[t + 1]]["degree"] > 0)) for t in range(len(offs) - 1)])
     gflops = float(rows * np.sum(opn * (1 + nconst) + 3 + 2 * nconst))
     cpu = None if args.no_cpu else cpu_c4_baseline(nodes, offs, opts, X, y, args.cpu_seconds)
-    fin = np.isfinite(base)
     # HBM bytes of the profiled gradient variant (scripts/pmc_grad.sh over scripts/grad_bench.py: the
     # same 512 x 100k population, one full loss + gradient launch)
     gname = "srhip::grad_kernel<double, 4, 2, 0, true, 2>"
     gtraffic, gvalu, gsrc = pmc_summary(gname, "*pmc_grad_c4*.json")
-    print(json.dumps({
-        "metric": "C4 batched constant optimisation: wall time per optimize_constants over the population",
-        "value": dt * 1e3, "unit": "ms", "higher_is_better": False, "n_gpus": 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt * 1e3, "dtype": "f64", "data": "synthetic (X ~ N(0,1) 5x100k; fixed-size-20 trees, >= 2 consts)",
-        "config": {"workload": f"C4: {ntrees} trees x {rows} rows Float64, BFGS(8) + 2 restarts",
-                   "ntrees": ntrees, "rows": rows, "nodes": int(st["total_nodes"])},
-        "objective_evals_per_s": float(np.sum(fcalls)) / dt,
-        "improved_trees": int(improved.sum()),
-        "mean_loss_before": float(np.mean(base[fin])), "mean_loss_after": float(np.mean(out[fin])),
-        # the mean is dominated by a few overflow-scale losses; the median shows the typical tree
-        "median_loss_before": float(np.median(base[fin])), "median_loss_after": float(np.median(out[fin])),
-        # a tree whose loss stays at ~1e250 fixes the arithmetic mean: the log-mean shows the whole population
-        "mean_log10_loss_before": float(np.mean(np.log10(np.maximum(base[fin], 1e-300)))),
-        "mean_log10_loss_after": float(np.mean(np.log10(np.maximum(out[fin], 1e-300)))),
+    return {
         "grad_launch_ms": gdt * 1e3,
         "grad_node_row_evals_per_s": st["total_nodes"] * rows / gdt,
         "roofline": {"bound": "valu", "kernel": "srhip::grad_kernel<double, KT, K, 0>", "kernel_ms": gk_ms,
@@ -924,7 +1008,7 @@ def bench_c4(args):
                      "traffic_kernel": gname if gtraffic is not None else None, "traffic_source": gsrc,
                      "valu_issue_util": gvalu},
         "cpu_baseline": cpu,
-    }))
+    }
 
 
 def _c4_cpu_worker(job):
@@ -1032,7 +1116,10 @@ def bench_search(args):
     front = res.pareto_frontier()
     best = float(min(m.loss for m in front))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"frontier_loss": np.array([m.loss for m in front], np.float64),
+                                         "frontier_nodes": np.array([srhip.count_nodes(m.tree) for m in front])})
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_search_baseline(args, c1, X, y, opts, iters, dt, skw)
     if rank == 0:
         print(json.dumps({

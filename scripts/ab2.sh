@@ -5,6 +5,8 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab
 export TMPDIR=/tmp
+# (--full: the runs below read what the bench measures beside its headline figure)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for rep in $(seq 1 ${REPS:-3}); do
   for spec in ${BUILDS}; do
     b=${spec%%:*}

@@ -14,7 +14,7 @@ step smoke
 timeout -k 10 240 python -u -c "import __graft_entry__ as g; g.smoke()" > $F/smoke.log 2>&1 || exit $?
 tail -1 $F/smoke.log
 step c4
-timeout -k 10 600 python -u bench.py --config c4 > $F/bench_c4.log 2>&1 || exit $?
+timeout -k 10 600 python -u bench.py --full --config c4 > $F/bench_c4.log 2>&1 || exit $?
 tail -1 $F/bench_c4.log > $F/bench_c4.json
 step grad_bench
 timeout -k 10 120 python3 scripts/grad_bench.py 20 > $F/grad_bench.log 2>&1 || exit $?

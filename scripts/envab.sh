@@ -4,6 +4,8 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/envab
 export TMPDIR=/tmp
+# (--full: the runs below read what the bench measures beside its headline figure)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 IFS=';' read -ra SETS <<< "${ENVS}"
 for rep in $(seq 1 ${REPS:-3}); do
   i=0

@@ -16,7 +16,7 @@ step smoke
 timeout -k 10 240 python -u -c "import __graft_entry__ as g; g.smoke()" > $F/smoke.log 2>&1 || exit $?
 tail -1 $F/smoke.log
 step c2
-timeout -k 10 400 python -u bench.py > $F/bench_c2.log 2>&1 || exit $?
+timeout -k 10 400 python -u bench.py --full > $F/bench_c2.log 2>&1 || exit $?
 tail -1 $F/bench_c2.log > $F/bench_c2.json
 step trace
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $F/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 30 --no-cpu --headline-only > $F/prof.log 2>&1 || exit $?
@@ -30,16 +30,16 @@ step rowshard
 timeout -k 10 300 python -u bench.py --mode rowshard --steps 10 --warmup 5 > $F/rowshard_n1.log 2>&1 || exit $?
 tail -1 $F/rowshard_n1.log > $F/rowshard_n1.json
 step c4
-timeout -k 10 600 python -u bench.py --config c4 > $F/bench_c4.log 2>&1 || exit $?
+timeout -k 10 600 python -u bench.py --full --config c4 > $F/bench_c4.log 2>&1 || exit $?
 tail -1 $F/bench_c4.log > $F/bench_c4.json
 step pmc_grad
 rm -rf gpurun_out/pmcg; bash scripts/pmc_grad.sh > $F/pmc_grad.log 2>&1 || exit $?
 python3 scripts/pmc_step.py gpurun_out/pmcg 8 grad_kernel --json $F/pmc_grad_c4.json > /dev/null
 step c1
-timeout -k 10 400 python -u bench.py --config c1 > $F/bench_c1.log 2>&1 || exit $?
+timeout -k 10 400 python -u bench.py --full --config c1 > $F/bench_c1.log 2>&1 || exit $?
 tail -1 $F/bench_c1.log > $F/bench_c1.json
 step c3
-timeout -k 10 400 python -u bench.py --config c3 > $F/bench_c3.log 2>&1 || exit $?
+timeout -k 10 400 python -u bench.py --full --config c3 > $F/bench_c3.log 2>&1 || exit $?
 tail -1 $F/bench_c3.log > $F/bench_c3.json
 step multi
 bash scripts/multi_rehearsal.sh > $F/multi.log 2>&1 || exit $?

@@ -12,7 +12,7 @@ step smoke
 timeout -k 10 240 python -u -c "import __graft_entry__ as g; g.smoke()" > $F/smoke.log 2>&1 || exit $?
 tail -1 $F/smoke.log
 step c2
-timeout -k 10 400 python -u bench.py > $F/bench_c2.log 2>&1 || exit $?
+timeout -k 10 400 python -u bench.py --full > $F/bench_c2.log 2>&1 || exit $?
 tail -1 $F/bench_c2.log > $F/bench_c2.json
 step trace
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $F/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 30 --no-cpu --headline-only > $F/prof.log 2>&1 || exit $?
@@ -26,9 +26,9 @@ step coalescer
 SECONDS_PER_RUN=3 timeout -k 10 200 python -u scripts/coalescer_native.py c3 16 64 > $F/coalescer_c3.jsonl 2>&1 || exit $?
 SECONDS_PER_RUN=3 timeout -k 10 200 python -u scripts/coalescer_native.py c1 1 16 64 > $F/coalescer_c1.jsonl 2>&1 || exit $?
 step c3
-timeout -k 10 400 python -u bench.py --config c3 > $F/bench_c3.log 2>&1 || exit $?
+timeout -k 10 400 python -u bench.py --full --config c3 > $F/bench_c3.log 2>&1 || exit $?
 tail -1 $F/bench_c3.log > $F/bench_c3.json
 step c1
-timeout -k 10 400 python -u bench.py --config c1 > $F/bench_c1.log 2>&1 || exit $?
+timeout -k 10 400 python -u bench.py --full --config c1 > $F/bench_c1.log 2>&1 || exit $?
 tail -1 $F/bench_c1.log > $F/bench_c1.json
 echo done

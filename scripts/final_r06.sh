@@ -23,7 +23,7 @@ if want smoke; then
 fi
 if want c2; then
   step c2
-  timeout -k 10 400 python -u bench.py > $F/bench_c2.log 2>&1 || exit $?
+  timeout -k 10 400 python -u bench.py --full > $F/bench_c2.log 2>&1 || exit $?
   tail -1 $F/bench_c2.log > $F/bench_c2.json
 fi
 if want trace; then
@@ -49,7 +49,7 @@ if want rowshard; then
 fi
 if want c4; then
   step c4
-  timeout -k 10 600 python -u bench.py --config c4 > $F/bench_c4.log 2>&1 || exit $?
+  timeout -k 10 600 python -u bench.py --full --config c4 > $F/bench_c4.log 2>&1 || exit $?
   tail -1 $F/bench_c4.log > $F/bench_c4.json
 fi
 if want pmc_grad; then
@@ -59,12 +59,12 @@ if want pmc_grad; then
 fi
 if want c1; then
   step c1
-  timeout -k 10 400 python -u bench.py --config c1 > $F/bench_c1.log 2>&1 || exit $?
+  timeout -k 10 400 python -u bench.py --full --config c1 > $F/bench_c1.log 2>&1 || exit $?
   tail -1 $F/bench_c1.log > $F/bench_c1.json
 fi
 if want c3; then
   step c3
-  timeout -k 10 400 python -u bench.py --config c3 > $F/bench_c3.log 2>&1 || exit $?
+  timeout -k 10 400 python -u bench.py --full --config c3 > $F/bench_c3.log 2>&1 || exit $?
   tail -1 $F/bench_c3.log > $F/bench_c3.json
 fi
 if want multi; then

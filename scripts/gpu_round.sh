@@ -17,6 +17,8 @@ if [ -n "${ROWSHARD:-}" ]; then
 fi
 if [ -n "${BUILDS:-}" ]; then bash scripts/ab2.sh || exit $?; fi
 # BENCHES="c4:--config c4 --no-cpu;c2:": extra bench lines, name:args separated by ';'
+# (a line's args need --full for what the bench measures beside its headline figure: CPU baselines,
+# other step and launch forms, the fresh-population pipeline)
 if [ -n "${BENCHES:-}" ]; then
   IFS=';' read -ra items <<< "$BENCHES"
   for it in "${items[@]}"; do

@@ -5,6 +5,8 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/search
 export TMPDIR=/tmp
+# (--full: the runs below read what the bench measures beside its headline figure)
+BENCH_EXTRA="--full ${BENCH_EXTRA:-}"
 timeout -k 10 300 python -u -m pytest tests/test_gpu_search.py -v --timeout 240 --timeout-method thread > gpurun_out/search/tests.log 2>&1
 rc=$?; echo "search tests rc=$rc"; grep -E "PASS|FAIL|passed|failed" gpurun_out/search/tests.log | tail -8
 [ $rc -eq 0 ] || exit $rc

@@ -1,7 +1,8 @@
 """bench.py --gpus N: the rank plan and the launch wiring (CPU; no rank touches the GPU under
 --launch-check).  The driver's scaling run calls `python bench.py --gpus N` or launches the ranks
 itself with torch.distributed.run; both must end with N ranks, and a WORLD_SIZE that disagrees with
---gpus must fail instead of reporting a rank count that did not run."""
+--gpus must fail instead of reporting a rank count that did not run.  Also the options of a plain
+run (--steps, --full off by default) and the --dump-outputs writer."""
 import json
 import os
 import subprocess
@@ -103,3 +104,48 @@ def test_native_selfcheck_keeps_or_drops_the_native_exchange():
     finally:
         if own:
             dist.destroy_process_group()
+
+
+def test_full_is_off_by_default_and_steps_are_the_timed_steps():
+    """A plain run does only what the headline needs: --full is an option, off by default; --steps is
+    the number of timed steps (c1 / c3: search iterations, unless --iterations says otherwise)."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d" and a.steps == 20
+    assert bench.parse(["--config", "c1", "--steps", "3"]).iterations == 3
+    assert bench.parse(["--config", "c3", "--steps", "3", "--iterations", "2"]).iterations == 2
+    assert bench.parse(["--config", "c1"]).iterations == 0  # (bench_search's own default)
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one .npy per array; float64 stays, everything else becomes float32; every file is
+    finite -- a floating-point output's non-finite entries are 0 in <name>.npy and classed in
+    <name>_nonfinite.npy (1 +Inf, 2 -Inf, 3 NaN), the two files together restoring it exactly; an output
+    past 2^20 elements is a fixed, seeded sample (the same elements from run to run, and in both of its files)."""
+    import numpy as np
+
+    big = np.arange(3 << 20, dtype=np.float64)
+    big[::5] = np.inf
+    arrays = {"losses": np.array([1.5, np.inf, np.nan, -np.inf, -0.25]), "did_succeed": np.array([True, False, True]),
+              "fcalls": np.array([3, 4], np.int64), "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["big.npy", "big_nonfinite.npy", "did_succeed.npy", "fcalls.npy", "losses.npy",
+                           "losses_nonfinite.npy"]
+    assert all(np.all(np.isfinite(a)) and a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["losses.npy"].dtype == np.float64 and got["losses.npy"].tolist() == [1.5, 0.0, 0.0, 0.0, -0.25]
+    assert got["losses_nonfinite.npy"].tolist() == [0.0, 1.0, 3.0, 2.0, 0.0]
+    back = got["losses.npy"].copy()
+    for code, v in ((1, np.inf), (2, -np.inf), (3, np.nan)):
+        back[got["losses_nonfinite.npy"] == code] = v
+    assert back.tobytes() == arrays["losses"].tobytes()
+    assert got["did_succeed.npy"].dtype == np.float32 and got["did_succeed.npy"].tolist() == [1.0, 0.0, 1.0]
+    assert got["fcalls.npy"].dtype == np.float32 and got["fcalls.npy"].tolist() == [3.0, 4.0]
+    assert got["big.npy"].dtype == np.float64 and got["big.npy"].shape == got["big_nonfinite.npy"].shape == (1 << 20,)
+    fin = got["big_nonfinite.npy"] == 0  # a sample of big's own elements, in order; every fifth was +Inf
+    assert np.all(np.diff(got["big.npy"][fin]) > 0) and np.all(got["big.npy"][fin] % 5 != 0)
+    assert np.all(got["big.npy"][~fin] == 0) and np.all(got["big_nonfinite.npy"][~fin] == 1)
+    assert 0.15 < np.mean(~fin) < 0.25
+    assert got["big.npy"].tobytes() == np.load(tmp_path / "b" / "big.npy").tobytes()
