@@ -173,6 +173,19 @@ int srhip_eval_loss(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program
                     const srhip_loss* loss, const int64_t* idx, int64_t nidx,
                     double* out_loss, uint8_t* out_ok);
 
+/* srhip_eval_loss with one row subset per tree: tree t is evaluated on rows
+ * rows[row_offsets[t] .. row_offsets[t+1]) (0-based, duplicates allowed, sets may differ in length).
+ * out_loss[t] / out_ok[t] are exactly (same bits) what srhip_eval_loss returns for tree t alone
+ * with idx = that set.  The batching mode's fresh minibatch per score (reference:
+ * src/LossFunctions.jl:114-127) for a whole population in ONE launch and one synchronisation: each
+ * wavefront gathers its tree's rows from the resident dataset itself.  Sets longer than what a wave
+ * can stage (40 KB of the set's feature, y and w columns: 1024 rows for Float32 data with 8 features)
+ * are evaluated one by one through srhip_eval_loss inside the same call.  srhip_last_kernel_ms reports
+ * the rowsets kernel, srhip_last_work the node-rows over the sets. */
+int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog,
+                            const srhip_loss* loss, const int64_t* row_offsets /*[ntrees+1]*/,
+                            const int64_t* rows, double* out_loss, uint8_t* out_ok);
+
 /* srhip_eval_loss in two halves, for callers that keep the device busy across populations (the
  * reference scores populations from concurrent tasks: Threads.@spawn per population,
  * src/SearchUtils.jl:121-122, @threads_if in src/SingleIteration.jl:112).  _submit queues the

@@ -4,8 +4,10 @@
 // src/Mutate.jl:268-274) from every population task at once (src/SearchUtils.jl:121-122).  One
 // launch per tree would leave the GPU idle between tiny kernels, so island threads submit here
 // and block; worker threads turn whatever is queued into one program and one srhip_eval_loss
-// launch (per distinct row subset).  Per-tree results of the interpreter do not depend on which
-// other trees share the launch, so a coalesced score equals the single-tree score bit for bit.
+// launch -- plus, for the requests that carry a row subset (the batching mode's fresh minibatch per
+// score), one program and one srhip_eval_loss_rowsets launch in which every tree reads its own rows.
+// Per-tree results of the interpreter do not depend on which other trees share the launch, so a
+// coalesced score equals the single-tree score bit for bit.
 //
 // Workers (SRHIP_COALESCE_WORKERS, default 2): each owns a context (the caller's for worker 0, its
 // own stream on the same device for the others) and a long-lived slot program, and takes the next
@@ -19,7 +21,6 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -95,8 +96,9 @@ namespace {
 // into its device buffers, which only grow -- no allocation, free or program object per flush (a
 // hipFree synchronises the whole device), and the upload is not synchronised separately: the
 // evaluation that follows on the same stream synchronises once, at its end.
+// rows == nullptr: every tree on the whole dataset; else tree t on rows[row_offs[t] .. row_offs[t + 1]).
 int run_slot_program(srhip_batcher* b, Worker& w, std::vector<srhip_node>&& nodes, std::vector<int64_t>&& offs,
-                     const std::vector<int64_t>& idx, double* loss, uint8_t* ok) {
+                     const std::vector<int64_t>* row_offs, const std::vector<int64_t>* rows, double* loss, uint8_t* ok) {
   srhip_program& P = *w.slot;
   P.ntrees = (int32_t)offs.size() - 1;
   P.nodes = std::move(nodes);
@@ -105,13 +107,14 @@ int run_slot_program(srhip_batcher* b, Worker& w, std::vector<srhip_node>&& node
   if (rc) return rc;
   rc = upload_program(P, false, true);  // uploaded with the launch's tree order, one copy
   if (rc) return rc;
-  return srhip_eval_loss(w.ctx, b->ds, &P, &b->loss, idx.empty() ? nullptr : idx.data(), (int64_t)idx.size(), loss,
-                         ok);
+  if (rows) return srhip_eval_loss_rowsets(w.ctx, b->ds, &P, &b->loss, row_offs->data(), rows->data(), loss, ok);
+  return srhip_eval_loss(w.ctx, b->ds, &P, &b->loss, nullptr, 0, loss, ok);
 }
 
-// One launch over the trees of `reqs` (same row subset); results in request order.
-void launch_group(srhip_batcher* b, Worker& w, const std::vector<Request*>& reqs, std::vector<std::pair<Request*, Result>>& out,
-                  double& kernel_ms) {
+// One launch over the trees of `reqs` -- all without a row subset, or (rowsets) each on its own;
+// results in request order.
+void launch_group(srhip_batcher* b, Worker& w, const std::vector<Request*>& reqs, bool rowsets,
+                  std::vector<std::pair<Request*, Result>>& out, double& kernel_ms) {
   const int32_t n = (int32_t)reqs.size();
   std::vector<srhip_node> nodes;
   std::vector<int64_t> offs(1, 0);
@@ -119,10 +122,18 @@ void launch_group(srhip_batcher* b, Worker& w, const std::vector<Request*>& reqs
     nodes.insert(nodes.end(), r->nodes.begin(), r->nodes.end());
     offs.push_back((int64_t)nodes.size());
   }
-  const std::vector<int64_t>& idx = reqs[0]->idx;
+  std::vector<int64_t> row_offs, rows;
+  if (rowsets) {
+    row_offs.push_back(0);
+    for (const Request* r : reqs) {
+      rows.insert(rows.end(), r->idx.begin(), r->idx.end());
+      row_offs.push_back((int64_t)rows.size());
+    }
+  }
   std::vector<double> loss(n);
   std::vector<uint8_t> ok(n);
-  int rc = run_slot_program(b, w, std::move(nodes), std::move(offs), idx, loss.data(), ok.data());
+  int rc = run_slot_program(b, w, std::move(nodes), std::move(offs), rowsets ? &row_offs : nullptr,
+                            rowsets ? &rows : nullptr, loss.data(), ok.data());
   b->n_launches++;
   if (rc == SRHIP_OK) {
     const double k = srhip_last_kernel_ms(w.ctx);
@@ -130,7 +141,7 @@ void launch_group(srhip_batcher* b, Worker& w, const std::vector<Request*>& reqs
   }
   if (rc != SRHIP_OK && n > 1 && rc != SRHIP_ERR_DEVICE) {
     // a malformed / unsupported tree fails the whole program: attribute errors per request
-    for (Request* r : reqs) launch_group(b, w, std::vector<Request*>{r}, out, kernel_ms);
+    for (Request* r : reqs) launch_group(b, w, std::vector<Request*>{r}, rowsets, out, kernel_ms);
     return;
   }
   const std::string err = rc == SRHIP_OK ? std::string() : std::string(srhip_last_error());
@@ -148,13 +159,15 @@ void launch_group(srhip_batcher* b, Worker& w, const std::vector<Request*>& reqs
 
 void srhip_batcher::flush(Worker& w, std::vector<Request>& batch) {
   const auto t0 = std::chrono::steady_clock::now();
-  // group by row subset (most searches: one group, idx empty)
-  std::map<std::vector<int64_t>, std::vector<Request*>> groups;
-  for (Request& r : batch) groups[r.idx].push_back(&r);
+  // two groups at most: the requests over the whole dataset (most searches: all of them), and those
+  // that carry a row subset, each tree on its own rows in one launch
+  std::vector<Request*> whole, subsets;
+  for (Request& r : batch) (r.idx.empty() ? whole : subsets).push_back(&r);
   std::vector<std::pair<Request*, Result>> out;
   out.reserve(batch.size());
   double kms = 0.0;
-  for (auto& g : groups) launch_group(this, w, g.second, out, kms);
+  if (!whole.empty()) launch_group(this, w, whole, false, out, kms);
+  if (!subsets.empty()) launch_group(this, w, subsets, true, out, kms);
   const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   {
     std::lock_guard<std::mutex> lk(mu);

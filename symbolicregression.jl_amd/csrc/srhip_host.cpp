@@ -3249,6 +3249,199 @@ int srhip_eval_loss(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program
   return run_eval(ctx, ds, prog, MODE_LOSS, loss, idx, nidx, out_loss, nullptr, out_ok);
 }
 
+// ---- srhip_eval_loss_rowsets: one row subset per tree, one launch (srhip_rowsets.hip) ----------------
+// Tree t of P alone on its set through the single-subset path (a one-tree program): the sets no wave
+// can stage, and the rare trees the fast bound leaves undecided (the precise pass lives there).
+static int rowset_single(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int32_t t, const srhip_loss* loss,
+                         const int64_t* rows, int64_t m, double* out_loss, uint8_t* out_ok) {
+  srhip_operators ops{(int32_t)P->binops.size(), (int32_t)P->unaops.size(), P->binops.data(), P->unaops.data()};
+  const int64_t offs[2] = {0, P->offsets[t + 1] - P->offsets[t]};
+  srhip_program* Q = nullptr;
+  int rc = srhip_program_create(ctx, P->dtype, P->nodes.data() + P->offsets[t], offs, 1, &ops, &Q);
+  if (rc) return rc;
+  rc = run_eval(ctx, ds, Q, MODE_LOSS, loss, rows, m, out_loss, nullptr, out_ok);
+  srhip_program_destroy(Q);
+  return rc;
+}
+
+int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
+                            const int64_t* row_offsets, const int64_t* rows, double* out_loss, uint8_t* out_ok) {
+  if (!row_offsets || !rows || !out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
+  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  if (!ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
+  const int32_t nt = P->ntrees;
+  if (row_offsets[0] != 0) return fail(SRHIP_ERR_INVALID, "row_offsets[0] must be 0");
+  for (int32_t t = 0; t < nt; ++t) {
+    if (row_offsets[t + 1] < row_offsets[t])
+      return fail(SRHIP_ERR_INVALID, "row_offsets[%d] = %lld < row_offsets[%d] = %lld", (int)t + 1,
+                  (long long)row_offsets[t + 1], (int)t, (long long)row_offsets[t]);
+    if (row_offsets[t + 1] == row_offsets[t]) return fail(SRHIP_ERR_INVALID, "tree %d has an empty row set", (int)t);
+    for (int64_t p = row_offsets[t]; p < row_offsets[t + 1]; ++p)
+      if (rows[p] < 0 || rows[p] >= ds->n)
+        return fail(SRHIP_ERR_INVALID, "tree %d: rows[%lld] (position %lld of its set) = %lld out of range [0, %lld)", (int)t,
+                    (long long)p, (long long)(p - row_offsets[t]), (long long)rows[p], (long long)ds->n);
+  }
+  if (nt == 0) return SRHIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int dtype = P->dtype;
+  const int64_t nf = ds->nfeat;
+  const bool weighted = ds->weighted;
+  const bool pdec = P->dec.size() == (size_t)nt;
+  if (dtype == SRHIP_F32 && (P->sbound.size() != 4 * (size_t)nt))
+    return fail(SRHIP_ERR_INVALID, "Float32 program without its +/- bounds");
+  // the sets a wave can stage go into the launch, longest and costliest first; the others run alone
+  const int cap = rowset_cap(dtype, nf, weighted), tile = 64 * rows_per_lane(dtype);
+  std::vector<int32_t> live, alone;
+  int64_t longest = 0;
+  for (int32_t t = 0; t < nt; ++t) {
+    if (pdec ? P->dec[t].static_fail : P->info[t].static_fail) continue;  // decided without a launch
+    const int64_t m = row_offsets[t + 1] - row_offsets[t];
+    if (m > cap) {
+      alone.push_back(t);
+    } else {
+      live.push_back(t);
+      longest = std::max(longest, m);
+    }
+  }
+  std::stable_sort(live.begin(), live.end(), [&](int32_t a, int32_t b) {
+    return (double)(row_offsets[a + 1] - row_offsets[a]) * P->info[a].cost > (double)(row_offsets[b + 1] - row_offsets[b]) * P->info[b].cost;
+  });
+  const int nl = (int)live.size();
+  ResultSet* const rs = &ctx->rs[0];
+  const FeatStat* fstat = nullptr;
+  const double* wsum = nullptr;
+  static thread_local std::vector<uint64_t> r_loss, r_chk, r_rows, r_fs;
+  if (nl > 0) {
+    const int ld_lds = (int)((longest + tile - 1) / tile * tile);
+    const int cpb = std::max(1, (ld_lds + loss_chunk(dtype) - 1) / loss_chunk(dtype));
+    const int64_t total = row_offsets[nt];
+    // [row_off | rows | order] in one copy
+    std::vector<int64_t> up((size_t)nt + 1 + (size_t)total + ((size_t)nl + 1) / 2);
+    memcpy(up.data(), row_offsets, ((size_t)nt + 1) * sizeof(int64_t));
+    memcpy(up.data() + nt + 1, rows, (size_t)total * sizeof(int64_t));
+    memcpy(up.data() + nt + 1 + total, live.data(), (size_t)nl * sizeof(int32_t));
+    HIP_TRY(ctx->vidx.ensure(up.size() * sizeof(int64_t)));
+    HIP_TRY(hipMemcpyAsync(ctx->vidx.p, up.data(), up.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (P->upload_pending) {  // the coalescer's deferred program image: uploaded here, no cached order survives
+      std::lock_guard<std::mutex> g(P->ord_mu);
+      HIP_TRY(P->d_prog.ensure(P->blob_off[6]));
+      HIP_TRY(hipMemcpyAsync(P->d_prog.p, P->blob.data(), P->blob_off[6], hipMemcpyHostToDevice, ctx->stream));
+      set_prog_pointers(*P);
+      P->upload_pending = false;
+      P->ord_key[0] = P->ord_key[1] = P->ord_key[2] = -1;
+      P->ord_goff.clear();
+    }
+    HIP_TRY(ctx->slab_loss.ensure((size_t)nl * cpb * 8));
+    HIP_TRY(ctx->slab_chk.ensure((size_t)nl * 8));
+    HIP_TRY(rs->h_loss.ensure((size_t)nt * 8, hipHostMallocCoherent));
+    HIP_TRY(rs->h_chk.ensure((size_t)nt * 8, hipHostMallocCoherent));
+    HIP_TRY(rs->h_rows.ensure((size_t)(nt + 1) * 8, hipHostMallocCoherent));
+    const size_t fs_bytes = (size_t)nt * std::max<int64_t>(1, nf) * sizeof(FeatStat);
+    HIP_TRY(ctx->h_rowsets.ensure(fs_bytes + (size_t)nt * sizeof(double), hipHostMallocCoherent));
+    RowsetArgs a{};
+    a.e.code = P->code_dev;
+    a.e.prog_off = P->off_dev;
+    a.e.order = (const int32_t*)((const int64_t*)ctx->vidx.p + nt + 1 + total);
+    a.e.X = ds->X.p;
+    a.e.y = ds->y.p;
+    a.e.w = weighted ? ds->w.p : nullptr;
+    a.e.slab_loss = ctx->slab_loss.p;
+    a.e.slab_chk = ctx->slab_chk.p;
+    a.e.ld = ld_lds;
+    a.e.ntrees = nl;
+    a.e.nfeat = P->maxfeat;
+    a.e.rb_rows = ld_lds;
+    a.e.nrb = 1;
+    a.e.nch = cpb;
+    a.e.cpb = cpb;
+    a.e.trees_per_group = 1;
+    a.e.loss_kind = loss->kind;
+    a.e.loss_p0 = loss->p0;
+    a.e.weighted = weighted ? 1 : 0;
+    a.e.has_y = 1;
+    a.e.max_steps = P->max_len;
+    a.e.fused = 1;
+    a.e.fused_loss = rs->h_loss.p;
+    a.e.fused_chk = dtype == SRHIP_I32 ? nullptr : rs->h_chk.p;
+    a.e.fused_rows = (int64_t*)rs->h_rows.p;
+    a.row_off = (const int64_t*)ctx->vidx.p;
+    a.rows = (const int64_t*)ctx->vidx.p + nt + 1;
+    a.src_ld = ds->ld;
+    a.nstage = (int32_t)nf;
+    a.ld_lds = ld_lds;
+    a.fstat = (FeatStat*)ctx->h_rowsets.p;
+    a.wsum = weighted ? (double*)((uint8_t*)ctx->h_rowsets.p + fs_bytes) : nullptr;
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(launch_rowsets(dtype, a, nl, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    rc = stream_wait(ctx);  // the call's one synchronisation
+    if (rc) return rc;
+    // the records, out of the device-written (coherent) buffers in bulk copies
+    r_loss.resize(nt);
+    r_chk.resize(nt);
+    r_rows.resize(nt);
+    r_fs.resize((fs_bytes + (size_t)nt * sizeof(double)) / 8);
+    memcpy(r_loss.data(), rs->h_loss.p, (size_t)nt * 8);
+    if (dtype != SRHIP_I32) memcpy(r_chk.data(), rs->h_chk.p, (size_t)nt * (dtype == SRHIP_F32 ? 4 : 8));
+    memcpy(r_rows.data(), rs->h_rows.p, (size_t)nt * 8);
+    memcpy(r_fs.data(), ctx->h_rowsets.p, r_fs.size() * 8);
+    fstat = (const FeatStat*)r_fs.data();
+    wsum = weighted ? (const double*)((const uint8_t*)r_fs.data() + fs_bytes) : nullptr;
+  }
+  // every launched tree decided on its own record: its set's rows, feature statistics and +/- bound
+  int64_t work[4] = {0, 0, 0, 0};
+  std::vector<double> sums(sums_len(nt, nf), 0.0);
+  double* const tail = sums.data() + 2 * (size_t)nt;
+  std::vector<int32_t> undecided;
+  const bool fast = pdec && !env_flag("SRHIP_DECIDE_SLOW");
+  for (int32_t t = 0; t < nt; ++t) {  // statically failing trees, and defaults
+    out_loss[t] = INFINITY;
+    out_ok[t] = 0;
+  }
+  for (int32_t t : live) {
+    const int64_t m = row_offsets[t + 1] - row_offsets[t];
+    View v{};
+    v.m = m;
+    v.stats = fstat + (size_t)t * nf;
+    for (int64_t f = 0; f < nf; ++f) {
+      tail[2 * f] = dtype == SRHIP_I32 ? 0.0 : v.stats[f].sum;
+      tail[2 * f + 1] = dtype == SRHIP_I32 ? 0.0 : (double)v.stats[f].nonfinite;
+    }
+    tail[2 * nf] = (double)m;
+    double chk = 0.0;
+    if (dtype == SRHIP_F32)
+      chk = skip_bound_apply(((const float*)r_chk.data())[t], P->sbound.data() + 4 * (size_t)t, feature_bound(v, nf));
+    else if (dtype == SRHIP_F64)
+      chk = ((const double*)r_chk.data())[t];
+    const double lsum = dtype == SRHIP_I32 ? (double)((const long long*)r_loss.data())[t] : ((const double*)r_loss.data())[t];
+    const int st = fast ? decide_fast(*P, t, nf, sums.data(), chk) : decide_info(P->info[t], dtype, nt, nf, sums.data(), chk);
+    if (st == 2) undecided.push_back(t);
+    out_ok[t] = st == 0 ? 1 : 0;
+    out_loss[t] = st == 0 ? lsum / (weighted ? wsum[t] : (double)m) : INFINITY;
+    const int64_t done = ((const int64_t*)r_rows.data())[t];
+    const int64_t nn = pdec ? P->dec[t].nnodes : P->info[t].nnodes, no = pdec ? P->dec[t].nops : P->info[t].nops;
+    work[0] += done * nn;
+    work[1] += m * nn;
+    work[2] += done * no;
+    work[3] += done;
+  }
+  alone.insert(alone.end(), undecided.begin(), undecided.end());
+  for (int32_t t : alone) {
+    rc = rowset_single(ctx, ds, P, t, loss, rows + row_offsets[t], row_offsets[t + 1] - row_offsets[t], out_loss + t, out_ok + t);
+    if (rc) return rc;
+    if (std::find(undecided.begin(), undecided.end(), t) == undecided.end())
+      for (int i = 0; i < 4; ++i) work[i] += ctx->work[i];
+  }
+  for (int i = 0; i < 4; ++i) ctx->work[i] = work[i];
+  if (nl > 0) {
+    ctx->last_ev0 = ctx->ev0;
+    ctx->last_ev1 = ctx->ev1;
+    ctx->timed = true;
+  }
+  return SRHIP_OK;
+}
+
 // srhip_eval_loss_submit / _wait: an evaluation whose launches return at once (queued on the context's
 // stream behind whatever is in flight there) and whose records, decisions and outputs are taken at wait.
 struct srhip_eval_ticket {

@@ -166,4 +166,24 @@ hipError_t launch_gather(int dtype, const void* X, const void* y, const void* w,
 hipError_t launch_feature_stats(int dtype, const void* X, int64_t ld, int64_t m, int nfeat, FeatStat* out,
                                 hipStream_t s);
 
+// One row subset per tree in one launch (srhip_rowsets.hip; srhip_eval_loss_rowsets).  e is a fused
+// single-row-block MODE_LOSS launch of one-tree groups over the plain program: X / y / w the RESIDENT
+// dataset (the kernel gathers from it), ld = rb_rows = ld_lds, cpb = the loss chunks of ld_lds rows,
+// order = the launched trees, ntrees = their number, nfeat = the program's feature columns.
+struct RowsetArgs {
+  EvalArgs e;
+  const int64_t* row_off;  // [program trees + 1] first position of each tree's set in rows
+  const int64_t* rows;     // the sets' dataset rows (0-based, in [0, n))
+  int64_t src_ld;          // padded rows of the resident X / y / w
+  int32_t nstage;          // feature columns staged and measured: the dataset's
+  int32_t ld_lds;          // rows of a wave's LDS region per column: whole tiles, >= the longest launched set
+  FeatStat* fstat;         // [program trees][nstage] each set's feature statistics (coherent host)
+  double* wsum;            // [program trees] each set's weight sum, position order (coherent host), or nullptr
+};
+// LDS bytes a wave may stage, and the longest set (whole tiles) that fits for a dataset of nfeat
+// feature columns: Float32 with 8 features, y and w: 1024 rows; four such waves per CU
+constexpr int ROWSET_LDS_BUDGET = 40 * 1024;
+int rowset_cap(int dtype, int64_t nfeat, bool weighted);
+hipError_t launch_rowsets(int dtype, const RowsetArgs& a, int nlaunch, hipStream_t s);
+
 }  // namespace srhip

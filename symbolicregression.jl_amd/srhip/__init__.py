@@ -12,6 +12,7 @@ from .api import (
     eval_loss,
     eval_loss_batch,
     eval_loss_batched,
+    eval_loss_rowsets_batch,
     eval_diff_tree_array,
     eval_grad_loss_batch,
     eval_grad_tree_array,
@@ -26,6 +27,7 @@ from .api import (
     score_func,
     score_func_batch,
     score_func_batched,
+    score_func_batched_batch,
     trees_equal,
     update_baseline_loss,
 )

@@ -88,6 +88,7 @@ SIGNATURES = {
     "srhip_program_set_constants": (ctypes.c_int, [_vp, _vp]),
     "srhip_program_get_constants": (ctypes.c_int, [_vp, _vp]),
     "srhip_eval_loss": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, _vp, _vp]),
+    "srhip_eval_loss_rowsets": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _vp, _vp, _vp]),
     "srhip_eval_predict": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "srhip_eval_loss_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, ctypes.POINTER(_vp)]),
     "srhip_eval_loss_wait": (ctypes.c_int, [_vp, _vp, _vp]),

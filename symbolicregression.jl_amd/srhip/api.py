@@ -133,6 +133,34 @@ def eval_loss_batch(trees, dataset: Dataset, options, regularization: bool = Tru
     return out, ok
 
 
+def eval_loss_rowsets_batch(trees, dataset: Dataset, options, idxs, regularization: bool = True):
+    """eval_loss_batch with a row subset of its own per tree (idxs[t], 0-based; the batching mode's
+    fresh minibatch per score, src/LossFunctions.jl:114-127), all trees in one device launch:
+    (loss[ntrees] float64, ok[ntrees]), element t exactly eval_loss_batch([trees[t]], ..., idx=idxs[t]).
+
+    A user loss_function, or an elementwise loss the device does not implement, takes the per-tree
+    loop through eval_loss(..., idx=idxs[t])."""
+    trees = _as_trees(trees)
+    idxs = list(idxs)
+    if len(idxs) != len(trees):
+        raise ValueError(f"{len(idxs)} row subsets for {len(trees)} trees")
+    if options.loss_function is not None or not is_device_loss(options.elementwise_loss):
+        out = np.array([eval_loss(t, dataset, options, regularization=regularization, idx=i)
+                        for t, i in zip(trees, idxs)], dtype=np.float64)
+        return out, np.isfinite(out)
+    ctx = _ctx(options)
+    prog = compile_trees(trees, options, dataset.X.dtype)
+    try:
+        out, ok = prog.eval_loss_rowsets(dataset.device(ctx), options.elementwise_loss, idxs)
+    finally:
+        prog.close()
+    if regularization and dataset.has_units():
+        L = dataset.loss_type.type
+        for t in np.nonzero(ok)[0]:
+            out[t] = float(L(out[t]) + dimensional_regularization(trees[t], dataset, options))
+    return out, ok
+
+
 def _eval_loss_batch_device(trees, dataset: Dataset, options, idx):
     ctx = _ctx(options)
     loss = options.elementwise_loss
@@ -244,6 +272,24 @@ def score_func_batch(dataset: Dataset, members, options, idx=None):
     losses = losses.astype(dataset.loss_type)
     scores = np.array([loss_to_score(L(l), dataset.use_baseline, dataset.baseline_loss, t, options)
                        for l, t in zip(losses, trees)], dtype=dataset.loss_type)
+    return scores, losses
+
+
+def score_func_batched_batch(dataset: Dataset, members, options, idxs=None, rng=None):
+    """score_func_batched over a whole population in one device launch, every member on a minibatch
+    of its own: (scores, losses) arrays in L like score_func_batch.  idxs=None draws
+    batch_sample(dataset, options, rng) once per member, in member order -- what a loop of
+    score_func_batched(dataset, member, options, rng=rng) draws -- so both leave rng in the same state
+    and return the same values."""
+    members = [members] if isinstance(members, Node) else list(members)
+    trees = _as_trees(members)
+    if idxs is None:
+        idxs = [batch_sample(dataset, options, rng) for _ in trees]
+    L = dataset.loss_type.type
+    losses, _ = eval_loss_rowsets_batch(trees, dataset, options, idxs)
+    losses = losses.astype(dataset.loss_type)
+    scores = np.array([loss_to_score(L(l), dataset.use_baseline, dataset.baseline_loss, m, options)
+                       for l, m in zip(losses, members)], dtype=dataset.loss_type)
     return scores, losses
 
 

@@ -110,6 +110,21 @@ class DeviceDataset:
             pass
 
 
+def pack_rowsets(idxs, ntrees=None):
+    """Ragged row subsets (one int array per tree) as the C ABI takes them: (offsets[ntrees + 1], rows),
+    both int64, tree t's rows at rows[offsets[t]:offsets[t + 1]].  An empty subset is an error."""
+    sets = [np.ascontiguousarray(i, dtype=np.int64).reshape(-1) for i in idxs]
+    if ntrees is not None and len(sets) != ntrees:
+        raise ValueError(f"{len(sets)} row subsets for {ntrees} trees")
+    for t, i in enumerate(sets):
+        if i.size == 0:
+            raise ValueError(f"row subset of tree {t} is empty")
+    offsets = np.zeros(len(sets) + 1, dtype=np.int64)
+    np.cumsum([i.size for i in sets], out=offsets[1:])
+    rows = np.concatenate(sets) if sets else np.zeros(0, dtype=np.int64)
+    return offsets, rows
+
+
 class Program:
     """A compiled batch of trees (bytecode resident on the device).
 
@@ -159,6 +174,18 @@ class Program:
         idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
         check(_lib.load().srhip_eval_loss(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls), ptr(idxa),
                                           0 if idxa is None else len(idxa), ptr(out), ptr(ok)))
+        return out, ok.astype(bool)
+
+    def eval_loss_rowsets(self, ds: DeviceDataset, loss, idxs):
+        """srhip_eval_loss_rowsets: tree t on its own row subset idxs[t] (0-based int arrays, one per tree,
+        duplicates allowed, lengths may differ), all in one launch; (loss[T], ok[T]) with the bits of
+        eval_loss(ds, loss, idx=idxs[t]) on tree t alone."""
+        offsets, rows = pack_rowsets(idxs, self.ntrees)
+        out = np.empty(self.ntrees, dtype=np.float64)
+        ok = np.empty(self.ntrees, dtype=np.uint8)
+        ls = loss.c_struct()
+        check(_lib.load().srhip_eval_loss_rowsets(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls),
+                                                  ptr(offsets), ptr(rows), ptr(out), ptr(ok)))
         return out, ok.astype(bool)
 
     def eval_loss_submit(self, ds: DeviceDataset, loss, idx=None) -> "EvalTicket":
