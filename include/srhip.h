@@ -348,6 +348,48 @@ int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srh
                                     double* starts_out, double* out_loss, uint8_t* out_improved,
                                     int64_t* out_fcalls);
 
+/* srhip_eval_loss_grad with one row subset per tree (row_offsets / rows as srhip_eval_loss_rowsets:
+ * 0-based rows, duplicates allowed, sets may differ in length; empty sets, non-monotone offsets,
+ * out-of-range rows and null pointers are SRHIP_ERR_INVALID naming the tree and the position; Int32
+ * programs are SRHIP_ERR_UNSUPPORTED).  out_loss[t], tree t's slice of out_grad and out_ok[t] are exactly
+ * (same bits) what srhip_eval_loss_grad returns for tree t alone, in a one-tree program, with idx = its
+ * set.  The objective of the batching mode's optimize_constants, where every member has a minibatch of
+ * its own (src/ConstantOptimization.jl:14-17 batch_sample per member, :48 its idx in f), for a whole
+ * population in one launch: the sets are gathered once into a packed device buffer, one wavefront per
+ * (tree, constant chunk) copies its set into LDS and walks it in the 256-row blocks of the single-idx
+ * kernel, combining the block records in that path's reduction order.  The derived view of the
+ * single-idx path is off below 8192 rows, so it never applies to a staged set.  Sets longer than a wave
+ * can stage (40 KB of the set's feature, y and w columns, in whole 256-row blocks: 1536 rows for Float32
+ * data with 5 features, 768 for Float64) go through srhip_eval_loss_grad one by one inside the same
+ * call.  srhip_last_kernel_ms reports the row-set gradient kernel. */
+int srhip_eval_loss_grad_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* prog,
+                                 const srhip_loss* loss, const int64_t* row_offsets /*[ntrees+1]*/,
+                                 const int64_t* rows, double* out_loss, double* out_grad,
+                                 uint8_t* out_ok);
+
+/* srhip_optimize_constants_starts with one row subset per tree: optimize_constants in batching mode
+ * (src/ConstantOptimization.jl:11-81, where :14-17 draws batch_sample(dataset, options) per member and
+ * the member's BFGS / Newton run, its restarts and its re-score all use that idx, :48, :72) for a whole
+ * population in one call, one launch per optimiser round over every tree still active.  For every tree,
+ * out_loss[t], out_improved[t], out_fcalls[t], the constants left in prog and its slice of starts_out
+ * are exactly (same bits) what srhip_optimize_constants_starts returns for tree t alone, with idx = its
+ * set and opt->seed = tree_seeds[t].
+ *   tree_seeds (nullable): [ntrees] the seed of tree t's own generator (NULL: opt->seed + t); its restart
+ *              points are drawn from that generator and a fresh normal distribution, start-major and then
+ *              constant by constant -- the sequence of the one-tree call;
+ *   starts_in / starts_out (nullable): the layout of srhip_optimize_constants_starts
+ *              ([nrestarts][sum nconst]); starts_in replaces the draws.
+ * Baseline and final re-score are one srhip_eval_loss_rowsets launch each; acceptance and out_fcalls
+ * follow srhip_optimize_constants.  Row-set conventions, validation and the handling of sets no wave
+ * can stage (the single-idx optimiser on that tree, inside the call) as srhip_eval_loss_grad_rowsets;
+ * a failed call leaves prog's constants unchanged. */
+int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* prog,
+                                     const srhip_loss* loss, const int64_t* row_offsets /*[ntrees+1]*/,
+                                     const int64_t* rows, const srhip_optim_options* opt,
+                                     const uint64_t* tree_seeds /*[ntrees], nullable*/,
+                                     const double* starts_in /*nullable*/, double* starts_out /*nullable*/,
+                                     double* out_loss, uint8_t* out_improved, int64_t* out_fcalls);
+
 /* ---- measurement hooks (bench / profiling) --------------------------------------------- */
 /* Device time (ms) of the last main kernel on this context -- the interpreter of srhip_eval_loss /
  * srhip_eval_predict, or the dual-number kernel of srhip_eval_loss_grad -- measured with HIP events

@@ -66,4 +66,37 @@ hipError_t launch_grad_reduce(int dtype, int kt, const double* slab, int nrb, in
 hipError_t launch_grad_derive(int dtype, const void* X, void* Xd, int64_t ld, const uint32_t* keys, int nd,
                               hipStream_t s);
 
+// ---- one row subset per chunk (srhip_grad_rowsets.hip; srhip_eval_loss_grad_rowsets and the optimiser
+// behind srhip_optimize_constants_rowsets) ---------------------------------------------------------
+// A chunk is (program slot, first constant c0, tree whose row set it reads).  The sets are packed once
+// per call by launch_grad_rowsets_pack: set t at element offset set_off[t], [nfeat + 1 (+ 1 weighted)]
+// columns (features, y, w) of ld_t = set_m[t] rounded up to GRAD_ROWSET_RB rows, the positions past the
+// set's end replicating its last row (weight 0) as a gathered view's padding does.
+constexpr int GRAD_ROWSET_RB = 256;  // the row block of grad_plan: a set's partial sums are per 256 rows
+struct GradRowsetArgs {
+  const Ins* code;          // gradient programs of all slots
+  const int32_t* prog_off;  // [slots]
+  const int32_t* chunks;    // [nchunks][3] (slot, c0, set), in launch order
+  const void* packed;       // the packed sets
+  const int64_t* set_off;   // [trees] element offset of each set in packed
+  const int32_t* set_m;     // [trees] rows of each set (1 .. the cap)
+  double* out;              // [nchunks][kt + 2] final records (coherent host memory)
+  int64_t ld;               // (unused: the tile body's derived-column reads, never taken here)
+  int32_t nchunks;
+  int32_t nfeat;
+  int32_t gd_nd;            // 0: row sets never use a derived view (it is off below 8192 rows)
+  int32_t loss_kind;
+  double loss_p0;
+  int32_t weighted;
+  int32_t max_steps;
+};
+// rows a wave can stage: whole 256-row blocks under ROWSET_LDS_BUDGET (0: the set's columns do not fit)
+int grad_rowset_cap(int dtype, int64_t nfeat, bool weighted);
+// max_ld: the longest padded set among the launch's chunks (sizes the per-wave LDS region)
+hipError_t launch_grad_rowsets(int dtype, int kt, const GradRowsetArgs& a, int max_ld, hipStream_t s);
+// the pack: rows[row_off[t] ..] of every column of the resident dataset -> packed (see above)
+hipError_t launch_grad_rowsets_pack(int dtype, const void* X, const void* y, const void* w, int64_t src_ld, int nfeat,
+                                    const int64_t* row_off, const int64_t* rows, const int64_t* set_off, int ntrees,
+                                    void* packed, hipStream_t s);
+
 }  // namespace srhip

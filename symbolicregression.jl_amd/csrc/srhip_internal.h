@@ -198,6 +198,7 @@ struct srhip_ctx {
   srhip::DevBuf slab_loss, slab_chk, slab_prec, order_prec;
   srhip::DevBuf vX, vy, vw, vidx, vstats;  // gathered views (batching idx)
   srhip::DevBuf g_chunks, g_slab, g_red;   // constant-gradient launches
+  srhip::DevBuf g_rs_packed, g_rs_meta;     // row-set gradient calls: the packed sets; [row_off | rows | set_off | set_m]
   srhip::DevBuf g_xd;                        // their derived view (features + derived columns)
   // what g_xd holds when built from a whole dataset (serial, ld, dtype, column base, spec): reused
   // by the next call over the same dataset and spec

@@ -14,6 +14,10 @@
 //   Differences from the reference, by design: exact (dual-number) gradients instead of Optim's
 //   finite differences, and Newton's Hessian as a central difference of those exact gradients instead
 //   of a second difference of losses -- parity is on the optimised loss, SURVEY.md 8(a) A13.
+// srhip_eval_loss_grad_rowsets / srhip_optimize_constants_rowsets: the same two with one row subset per
+//   tree (the batching mode's batch_sample per member, src/ConstantOptimization.jl:14-17): the optimiser's
+//   evaluation primitive runs every item on its tree's own set (eval_grad_items_rowsets over
+//   srhip_grad_rowsets.hip), everything above it is the one code path.
 #include <algorithm>
 #include <numeric>
 #include <chrono>
@@ -165,8 +169,24 @@ static int derived_view(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* 
   return SRHIP_OK;
 }
 
+// The row-set batch of one call (srhip_eval_loss_grad_rowsets / srhip_optimize_constants_rowsets): every
+// tree's own row subset, gathered once into a packed device buffer, with the per-set statistics the
+// decisions need.  Where a batch is given it replaces the View: item (slot, tree) is evaluated on tree's
+// set by grad_rowsets_kernel (eval_grad_items_rowsets) instead of on the view's rows.
+struct RowsetBatch {
+  const int64_t* row_off = nullptr;  // the caller's [ntrees + 1] offsets and row indices (validated)
+  const int64_t* rows = nullptr;
+  std::vector<uint8_t> staged;       // [ntrees] the set fits a wave's LDS region (others: the single-idx path)
+  std::vector<int32_t> m;            // [ntrees] rows of each set
+  std::vector<FeatStat> fstat;       // [ntrees][nfeat] each staged set's feature statistics
+  std::vector<double> wsum;          // [ntrees] each staged set's weight sum (weighted datasets)
+  const void* packed = nullptr;      // device: the packed sets (GradRowsetArgs)
+  const int64_t* d_set_off = nullptr;
+  const int32_t* d_set_m = nullptr;
+};
 static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
-                           const View& v, const std::vector<GradItem>& items, bool timed = true);
+                           const View& v, const std::vector<GradItem>& items, bool timed = true,
+                           const RowsetBatch* rb = nullptr);
 // Loss and gradient for `trees` at the program's current constants: f[t], g[coff[t] ..], ok[t]
 // (nullable; did_succeed -- a tree can succeed with an overflowing loss: f = Inf, ok = 1), plus the
 // items in `extra` (speculative slots, already instantiated; their instructions [spec_lo, spec_hi)
@@ -174,7 +194,8 @@ static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_progra
 static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss, const View& v,
                      const std::vector<int32_t>& trees, const std::vector<int64_t>& coff, double* f, double* g,
                      uint8_t* ok = nullptr, const std::vector<GradItem>* extra = nullptr, int64_t spec_lo = 0,
-                     int64_t spec_hi = -1, const uint8_t* value_only = nullptr, bool timed = true) {
+                     int64_t spec_hi = -1, const uint8_t* value_only = nullptr, bool timed = true,
+                     const RowsetBatch* rb = nullptr) {
   const double t0 = now_s();
   int rc = compile_grad_program(*P);
   g_t_compile += now_s() - t0;
@@ -192,7 +213,7 @@ static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, 
       memcpy(ctx->h_gspec.p, P->gcode.data() + spec_lo, nb);
       HIP_TRY(hipMemcpyAsync((Ins*)P->d_gcode.p + spec_lo, ctx->h_gspec.p, nb, hipMemcpyHostToDevice, ctx->stream));
     }
-    return eval_grad_items(ctx, ds, P, loss, v, items, timed);
+    return eval_grad_items(ctx, ds, P, loss, v, items, timed, rb);
   };
   rc = body();
   // a patched gradient program's upload (compile_grad_program) may still be in flight from P->gcode:
@@ -200,10 +221,171 @@ static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, 
   if (rc) (void)hipStreamSynchronize(ctx->stream);
   return rc;
 }
+// The evaluation primitive's second backend: every item on its tree's own row set (srhip_grad_rowsets.hip).
+// One single-wave workgroup per chunk (slot, c0, set), launched in descending set length x tree cost; the
+// waves write the final (kt + 2) records straight into the pinned staging, so a pass is one launch.  Each
+// item is decided on its own set's statistics (feature sums, non-finite counts, rows, weight sum); an
+// undecided item (a near-overflow sum) is settled by the precise pass over a view gathered from its set.
+static int eval_grad_items_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                                   const RowsetBatch& rb, const std::vector<GradItem>& items, bool timed) {
+  const int dtype = P->dtype;
+  const bool weighted = ds->weighted;
+  // the tangent width, as eval_grad_items picks it (no result depends on it)
+  int64_t cost4 = 0, cost8 = 0;
+  for (const GradItem& it : items) {
+    if (P->ginfo[it.slot].static_fail || it.value_only) continue;
+    const int nc = std::max(P->info[it.tree].nconst, 1);
+    cost4 += (int64_t)((nc + 3) / 4) * (3 + 4);
+    cost8 += (int64_t)((nc + GRAD_KT - 1) / GRAD_KT) * (3 + GRAD_KT);
+  }
+  const char* kte = env_get("SRHIP_GRAD_KT");
+  int kt = cost4 < cost8 ? 4 : GRAD_KT;
+  if (kte && (atoi(kte) == 4 || atoi(kte) == GRAD_KT)) kt = atoi(kte);
+  struct Pass {
+    int kt;
+    std::vector<int32_t> chunks, chunk_item;  // [nch][3] (slot, c0, set), and each chunk's item
+    const double* red = nullptr;
+    int max_ld = 0;
+  } pass[2];
+  pass[0].kt = kt;
+  pass[1].kt = 0;
+  for (size_t i = 0; i < items.size(); ++i) {
+    const GradItem& it = items[i];
+    *it.f = INFINITY;
+    if (it.ok) *it.ok = 0;
+    const int nc = P->info[it.tree].nconst;
+    if (!it.value_only)
+      for (int k = 0; k < nc; ++k) it.g[k] = 0.0;
+    if (P->ginfo[it.slot].static_fail) continue;
+    if (!rb.staged[it.tree]) return fail(SRHIP_ERR_INVALID, "tree %d: its row set is not staged", (int)it.tree);
+    Pass& ps = pass[it.value_only ? 1 : 0];
+    const int span = it.value_only ? 1 : std::max(nc, 1);
+    for (int c0 = 0; c0 < span; c0 += std::max(ps.kt, 1)) {
+      ps.chunks.push_back(it.slot);
+      ps.chunks.push_back(c0);
+      ps.chunks.push_back(it.tree);
+      ps.chunk_item.push_back((int32_t)i);
+    }
+  }
+  if (pass[0].chunk_item.empty() && pass[1].chunk_item.empty()) {  // a patched gradient program may still be uploading
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SRHIP_OK;
+  }
+  size_t chunk_n = 0;
+  for (Pass& ps : pass) {
+    const int nch = (int)ps.chunk_item.size();
+    if (nch == 0) continue;
+    std::vector<int32_t> by(nch);
+    std::iota(by.begin(), by.end(), 0);
+    auto weight = [&](int32_t c) { return (double)rb.m[ps.chunks[3 * c + 2]] * P->ginfo[ps.chunks[3 * c]].cost; };
+    std::stable_sort(by.begin(), by.end(), [&](int32_t x, int32_t y) { return weight(x) > weight(y); });
+    std::vector<int32_t> chunks2(ps.chunks.size()), item2(nch);
+    for (int pos = 0; pos < nch; ++pos) {
+      const int32_t k = by[pos];
+      for (int j = 0; j < 3; ++j) chunks2[3 * pos + j] = ps.chunks[3 * k + j];
+      item2[pos] = ps.chunk_item[k];
+      const int ld = (rb.m[ps.chunks[3 * k + 2]] + GRAD_ROWSET_RB - 1) / GRAD_ROWSET_RB * GRAD_ROWSET_RB;
+      ps.max_ld = std::max(ps.max_ld, ld);
+    }
+    ps.chunks.swap(chunks2);
+    ps.chunk_item.swap(item2);
+    chunk_n = std::max(chunk_n, ps.chunks.size());
+  }
+  HIP_TRY(ctx->g_chunks.ensure(chunk_n * sizeof(int32_t)));
+  bool first = true;
+  for (int pi = 0; pi < 2; ++pi) {
+    Pass& ps = pass[pi];
+    const int nch = (int)ps.chunk_item.size();
+    if (nch == 0) continue;
+    HIP_TRY(ctx->h_gred[pi].ensure((size_t)nch * (ps.kt + 2) * sizeof(double), hipHostMallocCoherent));
+    HIP_TRY(ctx->h_gchunks[pi].ensure(ps.chunks.size() * sizeof(int32_t)));
+    memcpy(ctx->h_gchunks[pi].p, ps.chunks.data(), ps.chunks.size() * sizeof(int32_t));
+    // stream order: this copy follows the previous pass's kernel, which has read its chunk list
+    HIP_TRY(hipMemcpyAsync(ctx->g_chunks.p, ctx->h_gchunks[pi].p, ps.chunks.size() * sizeof(int32_t),
+                           hipMemcpyHostToDevice, ctx->stream));
+    GradRowsetArgs a{};
+    a.code = (const Ins*)P->d_gcode.p;
+    a.prog_off = (const int32_t*)P->d_goff.p;
+    a.chunks = (const int32_t*)ctx->g_chunks.p;
+    a.packed = rb.packed;
+    a.set_off = rb.d_set_off;
+    a.set_m = rb.d_set_m;
+    a.out = (double*)ctx->h_gred[pi].p;
+    a.ld = 0;
+    a.nchunks = nch;
+    a.nfeat = (int32_t)ds->nfeat;
+    a.gd_nd = 0;
+    a.loss_kind = loss->kind;
+    a.loss_p0 = loss->p0;
+    a.weighted = weighted ? 1 : 0;
+    a.max_steps = P->gmax_len;
+    if (first && timed) HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    first = false;
+    HIP_TRY(launch_grad_rowsets(dtype, ps.kt, a, ps.max_ld, ctx->stream));
+    ps.red = (const double*)ctx->h_gred[pi].p;
+  }
+  if (timed) HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = timed;
+  ctx->last_ev0 = ctx->ev0;
+  ctx->last_ev1 = ctx->ev1;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  // decisions: each item on its own set's statistics, in the partials layout decide_tree reads
+  const int64_t nf = ds->nfeat;
+  std::vector<double> sums(2 * (size_t)P->ntrees + 2 * nf + 1, 0.0);
+  double* const tail = sums.data() + 2 * (size_t)P->ntrees;
+  std::vector<int32_t> undecided_item;
+  for (const Pass& ps : pass) {
+    const int nch = (int)ps.chunk_item.size();
+    for (int c = 0; c < nch; ++c) {
+      const GradItem& it = items[ps.chunk_item[c]];
+      const int32_t c0 = ps.chunks[3 * c + 1];
+      const double* r = ps.red + (size_t)c * (ps.kt + 2);
+      const int nc = P->info[it.tree].nconst;
+      const double wsum = weighted ? rb.wsum[it.tree] : (double)rb.m[it.tree];
+      for (int j = 0; j < ps.kt && c0 + j < nc; ++j) it.g[c0 + j] = r[1 + j] / wsum;
+      if (c0 == 0) {
+        const FeatStat* fs = rb.fstat.data() + (size_t)it.tree * nf;
+        for (int64_t fi = 0; fi < nf; ++fi) {
+          tail[2 * fi] = fs[fi].sum;
+          tail[2 * fi + 1] = (double)fs[fi].nonfinite;
+        }
+        tail[2 * nf] = (double)rb.m[it.tree];
+        const int st = decide_tree(P->ginfo[it.slot], *P, nf, sums.data(), r[ps.kt + 1]);
+        *it.f = st == 1 ? INFINITY : r[0] / wsum;
+        if (it.ok) *it.ok = st != 1;
+        if (st == 2) undecided_item.push_back(ps.chunk_item[c]);
+      }
+    }
+  }
+  if (g_stats_on)
+    for (const GradItem& it : items) {
+      int64_t* c = g_items[it.value_only ? 1 : 0][items.size() > 64 ? 1 : 0];
+      c[0] += 1;
+      c[1] += !std::isfinite(*it.f);
+    }
+  // near-overflow sums (rare): the exact per-operator-node pass on a view made from the item's own set
+  for (int32_t ui : undecided_item) {
+    const GradItem& it = items[ui];
+    View v{};
+    int rc = make_view(ctx, ds, rb.rows + rb.row_off[it.tree], rb.m[it.tree], true, v);
+    if (rc) return rc;
+    uint8_t uok = 0;
+    const int32_t slot = it.slot;
+    rc = precise_decide(ctx, ds, P, v, &slot, 1, true, &uok);
+    if (rc) return rc;
+    if (!uok) {
+      *it.f = INFINITY;
+      if (it.ok) *it.ok = 0;
+    }
+  }
+  return SRHIP_OK;
+}
+
 // timed: HIP events around the gradient kernels (srhip_last_kernel_ms).  The optimiser's launches go
 // without: two timing events per launch cost C4 ~5 % (149-153 against 141-145 ms on one box).
 static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
-                           const View& v, const std::vector<GradItem>& items, bool timed) {
+                           const View& v, const std::vector<GradItem>& items, bool timed, const RowsetBatch* rb) {
+  if (rb) return eval_grad_items_rowsets(ctx, ds, P, loss, *rb, items, timed);
   const int dtype = P->dtype;
   const bool weighted = ds->weighted;
   const double wsum = weighted ? v.sum_w : (double)v.m;
@@ -503,7 +685,8 @@ int ls_update(LineSearch& L, double phi) {
 static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
                           const View& v, const std::vector<int32_t>& trees, const std::vector<int64_t>& coff,
                           int iterations, double g_tol, const std::vector<std::vector<double>>& starts,
-                          std::vector<double>& best_x, std::vector<double>& best_f, std::vector<int64_t>& fcalls) {
+                          std::vector<double>& best_x, std::vector<double>& best_f, std::vector<int64_t>& fcalls,
+                          const RowsetBatch* rb = nullptr) {
   enum { INIT = 0, TRIAL = 1, DONE = 2, HESS_P = 3, HESS_M = 4, GRADAT = 5 };
   const int nstarts = (int)starts.size();
   const size_t nall = best_x.size();
@@ -825,7 +1008,7 @@ static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program
     }
     const double t1 = now_s();
     int rc = eval_grad(ctx, ds, P, loss, v, act, coff, fe.data(), ge.data(), nullptr, &sitems, spec_lo, spec_hi,
-                       vonly.data(), /*timed=*/false);
+                       vonly.data(), /*timed=*/false, rb);
     if (rc) return rc;
     if (g_stats_on)  // SRHIP_OPTIM_TIMING=2: launch-size histogram
       g_hist[act.size() <= 1 ? 0 : act.size() <= 4 ? 1 : act.size() <= 16 ? 2 : act.size() <= 64 ? 3 : 4] += 1;
@@ -1252,6 +1435,283 @@ int srhip_optimize_constants(srhip_ctx* ctx, const srhip_dataset* ds, srhip_prog
                              uint8_t* out_improved, int64_t* out_fcalls) {
   return srhip_optimize_constants_starts(ctx, ds, P, loss, idx, nidx, opt, nullptr, nullptr, out_loss, out_improved,
                                          out_fcalls);
+}
+
+}  // extern "C"
+
+// ---- one row subset per tree: srhip_eval_loss_grad_rowsets / srhip_optimize_constants_rowsets ---------
+namespace {
+
+// srhip_eval_loss_rowsets' conventions and error texts
+int check_rowsets(const srhip_dataset* ds, int32_t nt, const int64_t* row_offsets, const int64_t* rows) {
+  if (!ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
+  if (row_offsets[0] != 0) return fail(SRHIP_ERR_INVALID, "row_offsets[0] must be 0");
+  for (int32_t t = 0; t < nt; ++t) {
+    if (row_offsets[t + 1] < row_offsets[t])
+      return fail(SRHIP_ERR_INVALID, "row_offsets[%d] = %lld < row_offsets[%d] = %lld", (int)t + 1,
+                  (long long)row_offsets[t + 1], (int)t, (long long)row_offsets[t]);
+    if (row_offsets[t + 1] == row_offsets[t]) return fail(SRHIP_ERR_INVALID, "tree %d has an empty row set", (int)t);
+    for (int64_t p = row_offsets[t]; p < row_offsets[t + 1]; ++p)
+      if (rows[p] < 0 || rows[p] >= ds->n)
+        return fail(SRHIP_ERR_INVALID, "tree %d: rows[%lld] (position %lld of its set) = %lld out of range [0, %lld)", (int)t,
+                    (long long)p, (long long)(p - row_offsets[t]), (long long)rows[p], (long long)ds->n);
+  }
+  return SRHIP_OK;
+}
+
+// The call's batch: the baseline through the rowsets evaluation (one launch; base_loss / base_ok), whose
+// per-set records (feature statistics, weight sums) are kept on the host, and every set a wave can stage
+// gathered once into the context's packed buffer.  Sets over the cap, statically failing trees (the
+// evaluation took no statistics of their sets) and a non-default SRHIP_GRAD_RB stay unstaged: the
+// single-idx path.
+int make_rowset_batch(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                      const int64_t* row_offsets, const int64_t* rows, RowsetBatch& rb, double* base_loss,
+                      uint8_t* base_ok) {
+  const int32_t nt = P->ntrees;
+  const int64_t nf = ds->nfeat;
+  const bool weighted = ds->weighted;
+  int rc = srhip_eval_loss_rowsets(ctx, ds, P, loss, row_offsets, rows, base_loss, base_ok);
+  if (rc) return rc;
+  rb.row_off = row_offsets;
+  rb.rows = rows;
+  rb.staged.assign(nt, 0);
+  rb.m.assign(nt, 0);
+  rb.fstat.assign((size_t)nt * std::max<int64_t>(1, nf), FeatStat{});
+  rb.wsum.assign(nt, 0.0);
+  const int cap = grad_rowset_cap(P->dtype, nf, weighted);
+  const bool pdec = P->dec.size() == (size_t)nt;
+  const bool rb256 = grad_plan(ctx, 1, 1).rb_rows == GRAD_ROWSET_RB;
+  const size_t fs_stride = (size_t)std::max<int64_t>(1, nf);
+  const size_t fs_bytes = (size_t)nt * fs_stride * sizeof(FeatStat);
+  const int64_t ncol = nf + 1 + (weighted ? 1 : 0);
+  const int64_t total = row_offsets[nt];
+  // [row_off | rows | set_off] int64, then set_m int32
+  std::vector<int64_t> meta((size_t)nt + 1 + (size_t)total + (size_t)nt + ((size_t)nt + 1) / 2);
+  int64_t* const h_set_off = meta.data() + nt + 1 + total;
+  int32_t* const h_set_m = (int32_t*)(h_set_off + nt);
+  memcpy(meta.data(), row_offsets, ((size_t)nt + 1) * sizeof(int64_t));
+  memcpy(meta.data() + nt + 1, rows, (size_t)total * sizeof(int64_t));
+  int64_t elems = 0;
+  int32_t nstaged = 0;
+  for (int32_t t = 0; t < nt; ++t) {
+    const int64_t m = row_offsets[t + 1] - row_offsets[t];
+    const bool sfail = pdec ? P->dec[t].static_fail : P->info[t].static_fail;
+    const bool st = rb256 && m <= cap && !sfail && !P->info[t].static_fail;
+    rb.m[t] = (int32_t)std::min<int64_t>(m, INT32_MAX);
+    h_set_m[t] = st ? (int32_t)m : 0;
+    h_set_off[t] = st ? elems : -1;
+    if (!st) continue;
+    rb.staged[t] = 1;
+    nstaged += 1;
+    elems += ncol * ((m + GRAD_ROWSET_RB - 1) / GRAD_ROWSET_RB * GRAD_ROWSET_RB);
+    // the rowsets evaluation's records of this set (it launched the tree: m <= its cap, no static failure)
+    const FeatStat* fs = (const FeatStat*)ctx->h_rowsets.p + (size_t)t * fs_stride;
+    for (int64_t f = 0; f < nf; ++f) rb.fstat[(size_t)t * nf + f] = fs[f];
+    if (weighted) rb.wsum[t] = ((const double*)((const uint8_t*)ctx->h_rowsets.p + fs_bytes))[t];
+  }
+  if (nstaged == 0) return SRHIP_OK;
+  const size_t es = dtype_size(P->dtype);
+  HIP_TRY(ctx->g_rs_meta.ensure(meta.size() * sizeof(int64_t)));
+  HIP_TRY(ctx->g_rs_packed.ensure((size_t)elems * es));
+  HIP_TRY(hipMemcpyAsync(ctx->g_rs_meta.p, meta.data(), meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  const int64_t* d_meta = (const int64_t*)ctx->g_rs_meta.p;
+  rb.packed = ctx->g_rs_packed.p;
+  rb.d_set_off = d_meta + nt + 1 + total;
+  rb.d_set_m = (const int32_t*)(rb.d_set_off + nt);
+  HIP_TRY(launch_grad_rowsets_pack(P->dtype, ds->X.p, ds->y.p, weighted ? ds->w.p : nullptr, ds->ld, (int)nf, d_meta,
+                                   d_meta + nt + 1, rb.d_set_off, nt, ctx->g_rs_packed.p, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));  // (meta is a local: its copy must be complete)
+  return SRHIP_OK;
+}
+
+// tree t of P as a program of its own (the single-idx path of sets no wave can stage)
+int one_tree_program(srhip_ctx* ctx, const srhip_program* P, int32_t t, srhip_program** Q) {
+  const srhip_operators ops{(int32_t)P->binops.size(), (int32_t)P->unaops.size(), P->binops.data(), P->unaops.data()};
+  const int64_t offs[2] = {0, P->offsets[t + 1] - P->offsets[t]};
+  return srhip_program_create(ctx, P->dtype, P->nodes.data() + P->offsets[t], offs, 1, &ops, Q);
+}
+
+}  // namespace
+
+extern "C" {
+
+int srhip_eval_loss_grad_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                                 const int64_t* row_offsets, const int64_t* rows, double* out_loss, double* out_grad,
+                                 uint8_t* out_ok) {
+  if (!row_offsets || !rows || !out_loss || !out_grad || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
+  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant gradients need Float32 / Float64");
+  const int32_t nt = P->ntrees;
+  rc = check_rowsets(ds, nt, row_offsets, rows);
+  if (rc) return rc;
+  if (nt == 0) return SRHIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  RowsetBatch rb;
+  std::vector<double> base(nt);
+  std::vector<uint8_t> base_ok(nt);
+  rc = make_rowset_batch(ctx, ds, P, loss, row_offsets, rows, rb, base.data(), base_ok.data());
+  if (rc) return rc;
+  const std::vector<int64_t> coff = const_offsets(*P);
+  // the unstaged sets first, each through the single-idx call on a one-tree program
+  std::vector<int32_t> staged;
+  for (int32_t t = 0; t < nt; ++t) {
+    if (rb.staged[t]) {
+      staged.push_back(t);
+      continue;
+    }
+    srhip_program* Q = nullptr;
+    rc = one_tree_program(ctx, P, t, &Q);
+    if (rc) return rc;
+    rc = srhip_eval_loss_grad(ctx, ds, Q, loss, rows + row_offsets[t], row_offsets[t + 1] - row_offsets[t], out_loss + t,
+                              out_grad + coff[t], out_ok + t);
+    srhip_program_destroy(Q);
+    if (rc) return rc;
+  }
+  if (staged.empty()) return SRHIP_OK;
+  P->g_want_derived = false;  // (off below 8192 rows in the single-idx path too)
+  const View none{};
+  return eval_grad(ctx, ds, P, loss, none, staged, coff, out_loss, out_grad, out_ok, nullptr, 0, -1, nullptr, true, &rb);
+}
+
+int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                                     const int64_t* row_offsets, const int64_t* rows, const srhip_optim_options* opt,
+                                     const uint64_t* tree_seeds, const double* starts_in, double* starts_out,
+                                     double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
+  if (!row_offsets || !rows || !opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
+  if (opt->iterations < 0 || opt->nrestarts < 0) return fail(SRHIP_ERR_INVALID, "negative iterations / restarts");
+  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant optimisation needs Float32 / Float64");
+  const int32_t nt = P->ntrees;
+  rc = check_rowsets(ds, nt, row_offsets, rows);
+  if (rc) return rc;
+  if (nt == 0) return SRHIP_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  // baseline = f(tree) with the evaluator itself (src/ConstantOptimization.jl:49), every tree on its own set
+  RowsetBatch rb;
+  std::vector<double> base(nt);
+  std::vector<uint8_t> base_ok(nt);
+  rc = make_rowset_batch(ctx, ds, P, loss, row_offsets, rows, rb, base.data(), base_ok.data());
+  if (rc) return rc;
+  P->g_want_derived = false;
+  const std::vector<int64_t> coff = const_offsets(*P);
+  const std::vector<double> x0 = get_all_consts(*P);
+  const int64_t nall = (int64_t)x0.size();
+  std::vector<int32_t> trees, alone;  // trees with constants, by path (nconst == 0: nothing to optimise, :35)
+  for (int32_t t = 0; t < nt; ++t)
+    if (P->info[t].nconst > 0 && !P->info[t].static_fail) (rb.staged[t] ? trees : alone).push_back(t);
+  std::vector<double> best_x = x0, best_f(nt, INFINITY);
+  std::vector<int64_t> fcalls(nt, 0);
+  const double g_tol = opt->g_tol > 0 ? opt->g_tol : 1e-8;
+  const bool f32 = P->dtype == SRHIP_F32;
+  // the starting points: x0, then nrestarts perturbed copies; tree t draws from a generator of its own
+  // (tree_seeds[t], or opt->seed + t) start-major, then constant by constant -- the sequence the one-tree
+  // call draws (srhip_optimize_constants_starts), with its Float32 rule.  Trees without constants or
+  // failing statically keep x0.
+  std::vector<std::vector<double>> starts(opt->nrestarts + 1, x0);
+  auto tree_seed = [&](int32_t t) { return tree_seeds ? tree_seeds[t] : opt->seed + (uint64_t)t; };
+  for (int32_t t = 0; t < nt; ++t) {
+    if (!(P->info[t].nconst > 0 && !P->info[t].static_fail)) continue;
+    std::mt19937_64 rng(tree_seed(t));
+    std::normal_distribution<double> randn(0.0, 1.0);
+    for (int start = 1; start <= opt->nrestarts; ++start)
+      for (int64_t k = coff[t]; k < coff[t + 1]; ++k) {
+        double xs;
+        if (starts_in) {
+          xs = starts_in[(int64_t)(start - 1) * nall + k];
+        } else if (f32) {
+          const float r = (float)randn(rng);
+          xs = (double)((float)x0[k] * (1.0f + 0.5f * r));
+        } else {
+          xs = x0[k] * (1.0 + 0.5 * randn(rng));
+        }
+        starts[start][k] = f32 ? (double)(float)xs : xs;
+      }
+  }
+  if (starts_out)
+    for (int start = 1; start <= opt->nrestarts; ++start)
+      std::copy(starts[start].begin(), starts[start].end(), starts_out + (int64_t)(start - 1) * nall);
+  auto restore = [&]() {
+    set_all_consts(*P, x0.data());
+    compile_program(*P);
+    upload_program(*P);
+  };
+  if (!trees.empty()) {
+    const View none{};
+    const double tb = now_s();
+    g_t_compile = g_t_eval = g_t_host = 0.0;
+    g_patch_scan_s = g_patch_copy_s = 0.0;
+    g_n_launch = 0;
+    g_stats_on = g_launch_log = false;
+    rc = bfgs_pipelined(ctx, ds, P, loss, none, trees, coff, opt->iterations, g_tol, starts, best_x, best_f, fcalls, &rb);
+    const char* te = getenv("SRHIP_OPTIM_TIMING");  // the single-idx entry point's line, for this path
+    if (te && *te && *te != '0')
+      fprintf(stderr,
+              "srhip optim rowsets: %.1f ms optimiser, %lld launches, eval_grad %.1f ms (compile/patch %.1f ms: "
+              "scan+recompile %.1f, snapshot+upload %.1f), set_consts %.1f ms\n",
+              1e3 * (now_s() - tb), (long long)g_n_launch, 1e3 * g_t_eval, 1e3 * g_t_compile, 1e3 * g_patch_scan_s,
+              1e3 * g_patch_copy_s, 1e3 * g_t_host);
+    if (rc) {
+      restore();
+      return rc;
+    }
+  }
+  // accept where the best minimum beats the baseline (:70-78)
+  std::vector<double> final_x = x0;
+  for (int32_t t = 0; t < nt; ++t) {
+    const bool better = best_f[t] < base[t];
+    out_improved[t] = better ? 1 : 0;
+    if (better)
+      for (int64_t k = coff[t]; k < coff[t + 1]; ++k) final_x[k] = best_x[k];
+  }
+  // the sets no wave can stage: the existing entry point on a one-tree program (its own view, baseline,
+  // optimiser run and acceptance), seeded with the tree's seed and given the tree's starts
+  for (int32_t t : alone) {
+    const int64_t nc = coff[t + 1] - coff[t];
+    std::vector<double> sin((size_t)opt->nrestarts * nc), cst;
+    for (int start = 1; start <= opt->nrestarts; ++start)
+      for (int64_t k = 0; k < nc; ++k) sin[(size_t)(start - 1) * nc + k] = starts[start][coff[t] + k];
+    srhip_program* Q = nullptr;
+    const srhip_operators ops{(int32_t)P->binops.size(), (int32_t)P->unaops.size(), P->binops.data(), P->unaops.data()};
+    // (the tree at x0: the optimiser above moved only the staged trees' constants)
+    std::vector<srhip_node> nd(P->nodes.begin() + P->offsets[t], P->nodes.begin() + P->offsets[t + 1]);
+    const int64_t offs[2] = {0, (int64_t)nd.size()};
+    rc = srhip_program_create(ctx, P->dtype, nd.data(), offs, 1, &ops, &Q);
+    if (rc == SRHIP_OK) {
+      srhip_optim_options o1 = *opt;
+      o1.seed = tree_seed(t);
+      double l1 = 0.0;
+      uint8_t imp = 0;
+      int64_t fc = 0;
+      rc = srhip_optimize_constants_starts(ctx, ds, Q, loss, rows + row_offsets[t], row_offsets[t + 1] - row_offsets[t], &o1,
+                                           opt->nrestarts > 0 ? sin.data() : nullptr, nullptr, &l1, &imp, &fc);
+      if (rc == SRHIP_OK) {
+        get_consts_rec(Q->nodes.data(), 0, cst);
+        for (int64_t k = 0; k < nc; ++k) final_x[coff[t] + k] = cst[k];
+        out_improved[t] = imp;
+        fcalls[t] = fc - imp;
+      }
+      srhip_program_destroy(Q);
+    }
+    if (rc) {
+      const std::string msg = last_error();
+      restore();
+      return fail(rc, "%s", msg.c_str());
+    }
+  }
+  set_all_consts(*P, final_x.data());
+  rc = compile_program(*P);
+  if (rc) return rc;
+  rc = upload_program(*P);
+  if (rc) return rc;
+  // the loss of the returned trees, by the evaluator (the reference re-scores accepted members): one launch
+  std::vector<uint8_t> ok(nt);
+  rc = srhip_eval_loss_rowsets(ctx, ds, P, loss, row_offsets, rows, out_loss, ok.data());
+  if (rc) return rc;
+  if (out_fcalls)
+    for (int32_t t = 0; t < nt; ++t) out_fcalls[t] = fcalls[t] + out_improved[t];
+  return SRHIP_OK;
 }
 
 }  // extern "C"

@@ -380,19 +380,28 @@ def update_baseline_loss(dataset: Dataset, options) -> None:
 
 
 # ---- constant optimisation ---------------------------------------------------------------------
-def eval_grad_loss_batch(trees, dataset: Dataset, options, idx=None):
+def eval_grad_loss_batch(trees, dataset: Dataset, options, idx=None, idxs=None):
     """Loss and its exact gradient w.r.t. each tree's constants (get_constants order), one launch:
     (loss[T], [grad per tree], ok[T]).  The loss-level counterpart of eval_grad_tree_array
-    (src/InterfaceDynamicExpressions.jl:118-124, variable=false)."""
+    (src/InterfaceDynamicExpressions.jl:118-124, variable=false).  idxs: one row subset per tree
+    (like eval_loss_rowsets_batch) instead of the shared idx, still one launch."""
     trees = _as_trees(trees)
+    if idxs is not None:
+        if idx is not None:
+            raise ValueError("idx and idxs are exclusive")
+        idxs = list(idxs)
+        if len(idxs) != len(trees):
+            raise ValueError(f"{len(idxs)} row subsets for {len(trees)} trees")
     prog = compile_trees(trees, options, dataset.X.dtype)
     try:
+        if idxs is not None:
+            return prog.eval_loss_grad_rowsets(dataset.device(_ctx(options)), options.elementwise_loss, idxs)
         return prog.eval_loss_grad(dataset.device(_ctx(options)), options.elementwise_loss, idx)
     finally:
         prog.close()
 
 
-def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None):
+def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None, idxs=None):
     """optimize_constants (src/ConstantOptimization.jl:11-81) for one member or a whole list at once.
 
     Members are PopMember-like objects (``.tree``, ``.loss``, ``.score``, ``.birth``) or bare Nodes.
@@ -402,7 +411,11 @@ def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None):
 
     Built-in distance losses: one batched device call (srhip_optimize_constants: dual-number
     gradients, Newton / BFGS per tree).  With ``options.batching`` every member draws its own
-    minibatch (src/ConstantOptimization.jl:14-16), so members are optimised one device call each.
+    minibatch (src/ConstantOptimization.jl:14-16); a member list is still optimised by one device call
+    (srhip_optimize_constants_rowsets: every tree on its own rows, one launch per optimiser round).  The
+    generator is consumed as a loop over the members would: first every member's ``batch_sample``, in
+    member order, then one seed per member, in member order -- and each member's outcome has the bits
+    of that loop.  ``idxs`` gives one row subset per member instead of the draws (no ``batch_sample``).
     A user ``loss_function`` (or a Python elementwise loss): host Newton / BFGS with finite
     differences over ``eval_loss`` (srhip.host_optim), whose evaluations run on the device."""
     from .node import get_constants, set_constants
@@ -414,13 +427,37 @@ def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None):
     rng = np.random.default_rng() if rng is None else rng
     eval_fraction = (options.batch_size / dataset.n) if options.batching else 1.0
     L = dataset.loss_type.type
-    if idx is not None or not options.batching:
+    per_member = idxs is not None or (idx is None and options.batching)  # a row subset for each member
+    if idxs is not None:
+        if idx is not None:
+            raise ValueError("idx and idxs are exclusive")
+        idxs = list(idxs)
+        if len(idxs) != len(mlist):
+            raise ValueError(f"{len(idxs)} row subsets for {len(mlist)} members")
+        groups = [([i], np.asarray(idxs[i])) for i in range(len(mlist))]
+    elif idx is not None or not options.batching:
         groups = [(list(range(len(mlist))), idx)]
     else:
         groups = [([i], batch_sample(dataset, options, rng)) for i in range(len(mlist))]
     num_evals = 0.0
+    rowset_results = None
+    if (per_member and not single and options.loss_function is None
+            and is_device_loss(options.elementwise_loss)):
+        # one subset per member of a list, device loss: one call for all of them
+        seeds = [int(rng.integers(0, 2**63 - 1)) for _ in groups]
+        prog = compile_trees(trees, options, dataset.X.dtype)
+        try:
+            losses, improved, fcalls = prog.optimize_constants_rowsets(
+                dataset.device(_ctx(options)), options.elementwise_loss, [g for _, g in groups],
+                iterations=options.optimizer_iterations, nrestarts=options.optimizer_nrestarts, seeds=seeds)
+            consts = prog.get_constants()
+        finally:
+            prog.close()
+        rowset_results = list(zip(improved, consts, losses, fcalls))
     for members_idx, gidx in groups:
-        if options.loss_function is not None or not is_device_loss(options.elementwise_loss):
+        if rowset_results is not None:
+            results = [rowset_results[i] for i in members_idx]
+        elif options.loss_function is not None or not is_device_loss(options.elementwise_loss):
             results = _optimize_constants_host(dataset, [trees[i] for i in members_idx], options, rng, gidx)
         else:
             seed = int(rng.integers(0, 2**63 - 1))

@@ -277,6 +277,52 @@ class Program:
             return out, imp.astype(bool), fc, sout
         return out, imp.astype(bool), fc
 
+    def eval_loss_grad_rowsets(self, ds: DeviceDataset, loss, idxs):
+        """srhip_eval_loss_grad_rowsets: tree t on its own row subset idxs[t] (as eval_loss_rowsets), all in
+        one launch; (loss[T], grads: list of per-tree arrays, ok[T]) with the bits of
+        eval_loss_grad(ds, loss, idx=idxs[t]) on tree t alone."""
+        offsets, rows = pack_rowsets(idxs, self.ntrees)
+        nconst = self.num_constants()
+        out = np.empty(self.ntrees, dtype=np.float64)
+        grad = np.empty(int(nconst.sum()), dtype=np.float64)
+        ok = np.empty(self.ntrees, dtype=np.uint8)
+        ls = loss.c_struct()
+        check(_lib.load().srhip_eval_loss_grad_rowsets(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls),
+                                                       ptr(offsets), ptr(rows), ptr(out), ptr(grad), ptr(ok)))
+        return out, np.split(grad, np.cumsum(nconst)[:-1]), ok.astype(bool)
+
+    def optimize_constants_rowsets(self, ds: DeviceDataset, loss, idxs, iterations=8, nrestarts=2, seeds=None, seed=0,
+                                   g_tol=1e-8, starts=None, return_starts=False):
+        """srhip_optimize_constants_rowsets: optimize_constants with tree t on its own row subset idxs[t], the
+        whole population in one call; updates this program's constants in place.
+
+        seeds: optional [T] seed of each tree's own restart generator (default seed + t).  starts /
+        return_starts as optimize_constants.  Every tree's outcome has the bits of
+        optimize_constants(idx=idxs[t], seed=seeds[t]) on tree t alone.  Returns (loss[T], improved[T],
+        fcalls[T]), plus the restart points used if return_starts."""
+        offsets, rows = pack_rowsets(idxs, self.ntrees)
+        opt = _lib.OptimOptions(int(iterations), int(nrestarts), int(seed) & (2**64 - 1), float(g_tol))
+        out = np.empty(self.ntrees, dtype=np.float64)
+        imp = np.empty(self.ntrees, dtype=np.uint8)
+        fc = np.empty(self.ntrees, dtype=np.int64)
+        ls = loss.c_struct()
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
+            if len(sd) != self.ntrees:
+                raise ValueError(f"{len(sd)} seeds for {self.ntrees} trees")
+        nall = int(self.num_constants().sum())
+        sin = None
+        if starts is not None:
+            sin = np.ascontiguousarray(starts, dtype=np.float64).reshape(int(nrestarts), nall)
+        sout = np.empty((int(nrestarts), nall), dtype=np.float64) if return_starts else None
+        check(_lib.load().srhip_optimize_constants_rowsets(
+            self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls), ptr(offsets), ptr(rows), ctypes.byref(opt),
+            ptr(sd), ptr(sin), ptr(sout), ptr(out), ptr(imp), ptr(fc)))
+        if return_starts:
+            return out, imp.astype(bool), fc, sout
+        return out, imp.astype(bool), fc
+
     # ---- row-sharded evaluation (include/srhip.h "row-sharded evaluation") ----------------------
     def chk_reduce_op(self) -> str:
         """How chk combines across shards: "max" (Float32) or "sum" (Float64 / Int32)."""
