@@ -414,6 +414,11 @@ int srhip_program_derived(const srhip_program* prog, int32_t* count, uint32_t* s
  * NULL): trees served from the cache, trees compiled, entries made (a tree gets an entry on its
  * second sighting; SRHIP_CODE_CACHE_EAGER=1: on its first). */
 int srhip_code_cache_stats(int64_t* hits, int64_t* misses, int64_t* inserts);
+/* The persistent launch's last-round plan, for tests: the parts of share `share` when
+ * `blocks` leftover row blocks of `units` units each are dealt to `nshares` >= blocks shares.  Writes
+ * up to two parts as (block, first unit, end unit) triples to out[6] and returns their number (0: an
+ * empty share), or a negative value for arguments out of range.  No device is needed. */
+int srhip_tail_share_parts(int32_t blocks, int32_t units, int32_t nshares, int32_t share, int32_t* out);
 
 /* ---- Cross-population request coalescer (8(b) "Threading") ----------------
  * The reference scores one tree per mutation from every population task concurrently

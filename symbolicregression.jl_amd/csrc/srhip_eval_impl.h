@@ -1169,13 +1169,14 @@ __device__ __attribute__((always_inline)) inline void derive_columns_tiles(const
 // ------------------------------------------------------------------------------------------------
 // One (row block, tree group) of the launch: stage the block, derive its columns, interpret the
 // group's trees over it.  rb = row block, gy = tree group (grid.y; 0 in persistent launches, whose
-// one group is the whole population).  gstride > 1 (a persistent launch's tail items): the group is
-// the order slots gslice, gslice + gstride, ... -- an interleaved 1/gstride of the population, so
-// the slices of a block cost about the same.
+// one group is the whole population).  gstride > 1 (a persistent launch's share parts, the probe's
+// interleaved groups): the group is the order slots whose unit slot % gstride lies in
+// [gslice, gslice + gw) -- tree index ti is slot (ti / gw) * gstride + gslice + ti % gw, ascending, so
+// still in descending cost -- an interleaved gw/gstride of the population.
 template <typename T, int R, int K, int MODE, bool XLDS>
 __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs& p, unsigned char* smem, const int rb,
                                                                  const int gy, const int gslice = 0,
-                                                                 const int gstride = 1) {
+                                                                 const int gstride = 1, const int gw = 1) {
   constexpr int WAVES = eval_waves(R, K);
   using O = OpsT<T>;
   using CT = typename Chk<T>::type;
@@ -1231,13 +1232,13 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
   __shared__ uint8_t failed_snap[SNAP ? FLAG_SNAP : 1];
   const int gb0 = p.group_off ? p.group_off[gy] : gy * p.trees_per_group;
   const int snap_base = gb0 + gslice;
-  const int snap_n = gstride > 1 ? (p.ntrees - gslice + gstride - 1) / gstride
+  const int snap_n = gstride > 1 ? tail_units_count(p.ntrees, gstride, gslice, gw)
                                  : (p.group_off ? p.group_off[gy + 1] - gb0 : min(p.trees_per_group, p.ntrees - gb0));
   if constexpr (SNAP) {
     if (p.early_exit)
       for (int i = tid_x(); i < min(snap_n, FLAG_SNAP); i += blockDim.x)
-        failed_snap[i] = __hip_atomic_load(p.fail_flag + snap_base + i * gstride, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT) == p.epoch;
+        failed_snap[i] = __hip_atomic_load(p.fail_flag + snap_base + (gw > 1 ? i / gw * gstride + i % gw : i * gstride),
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p.epoch;
   }
   __syncthreads();
   constexpr bool DERIVED = XLDS && !kIsInt<T> && MODE != MODE_PRECISE;
@@ -1255,7 +1256,7 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
   const int group_base = __builtin_amdgcn_readfirstlane(snap_base);
   int group_n = __builtin_amdgcn_readfirstlane(snap_n);
   if constexpr (MODE == MODE_PRECISE) {
-    // device-listed trees: this group's slots (group_base, + gstride, ...) that the list filled
+    // device-listed trees: this group's slots (group_base, + gstride, ...; gw = 1) that the list filled
     if (p.dev_count) {
       const int cnt = __builtin_amdgcn_readfirstlane(*p.dev_count);
       group_n = max(0, min(group_n, (cnt - group_base + gstride - 1) / gstride));
@@ -1280,7 +1281,7 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
     const int ti = tile_claims ? cl / ntiles : cl;
     const int tile0 = tile_claims ? cl - ti * ntiles : 0, tile_end = tile_claims ? tile0 + 1 : ntiles;
     KMARK(8 + wave, 11);
-    const int slot = group_base + ti * gstride;  // order slot (uniform)
+    const int slot = group_base + (gw > 1 ? ti / gw * gstride + ti % gw : ti * gstride);  // order slot (uniform)
     const int tree = __builtin_amdgcn_readfirstlane(p.order[slot]);
     const int pc0 = __builtin_amdgcn_readfirstlane(p.prog_off[tree]);
     const int max_steps = __builtin_amdgcn_readfirstlane(p.max_steps);
@@ -1604,9 +1605,10 @@ __global__ __launch_bounds__(64 * eval_waves(R, K)) void eval_kernel(EvalArgs p)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   KMARK(0, 1);
   if (p.debug_stop == 1) return;
-  // items [0, nfull): whole row blocks block0 .. block0 + nfull - 1; then tail_slices items per
-  // remaining row block, each an interleaved slice of the population (the last round of a launch
-  // in finer pieces: the workgroups end within a slice of each other, not within a block).
+  // items [0, nfull): whole row blocks block0 .. block0 + nfull - 1; then tail_shares items, the
+  // equal shares of the remaining tail_blocks row blocks' units (srhip_tail_shares.h: the last
+  // round of a launch ends on every workgroup at nearly the same time).  A share is one or two
+  // parts (row block, unit range); its second part runs as the loop's next pass, without a claim.
   // Grid launches run their one (blockIdx.x, blockIdx.y) item.  One call site: the interpreter
   // body is inlined once.
   __shared__ int claimed;
@@ -1632,28 +1634,48 @@ __global__ __launch_bounds__(64 * eval_waves(R, K)) void eval_kernel(EvalArgs p)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   }
   const int nfull = p.nrb - p.block0 - p.tail_blocks;
-  const int nitems = nfull + p.tail_blocks * p.tail_slices;
+  const int nitems = nfull + (p.tail_blocks > 0 ? p.tail_shares : 0);
+  int items = 0;                      // persistent launches: the items this workgroup claimed
+  int next_block = 0, next_units = 0; // a claimed share's second part (units [0, next_units)), if pending
   for (int it = 0;; ++it) {
-    int rb, gy = 0, gslice = 0, gstride = 1;
-    if (p.persistent) {
+    int rb, gy = 0, gslice = 0, gstride = 1, gw = 1;
+    if (p.persistent && next_units > 0) {
+      rb = next_block;
+      gstride = p.tail_slices;
+      gw = next_units;
+      next_units = 0;
+    } else if (p.persistent) {
       if (threadIdx.x == 0) claimed = atomicAdd(p.block_ctr, 1);
       __syncthreads();
       const int item = __builtin_amdgcn_readfirstlane(claimed);
       if (item >= nitems) {
         // the items this workgroup evaluated, added to block_ctr[1]: the reduction compares the launch's
         // total with its item count (a counter left non-zero would have skipped items) and clears it
-        if (threadIdx.x == 0 && it > 0) atomicAdd(p.block_ctr + 1, it);
+        if (threadIdx.x == 0 && items > 0) atomicAdd(p.block_ctr + 1, items);
         // every workgroup ends on one failing claim; the last of them (nitems + grid - 1) leaves the
         // counter at zero for the context's next persistent launch (no memset launch before it)
         if (threadIdx.x == 0 && item == nitems + (int)gridDim.x - 1)
           __hip_atomic_store(p.block_ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         break;
       }
-      const int q = item - nfull;
-      const bool whole = item < nfull;
-      rb = p.block0 + (whole ? item : nfull + q / p.tail_slices);
-      gslice = whole ? 0 : q % p.tail_slices;
-      gstride = whole ? 1 : p.tail_slices;
+      ++items;
+      rb = p.block0 + item;
+      if (item >= nfull) {
+        TailPart part[2];
+        const int nparts = tail_share_parts(p.tail_blocks, p.tail_slices, p.tail_shares, item - nfull, part);
+        if (nparts == 0) {  // fewer units than shares: nothing to evaluate, the item still counts
+          __syncthreads();  // (every wave has read `claimed`)
+          continue;
+        }
+        rb = p.block0 + nfull + part[0].block;
+        gslice = part[0].u0;
+        gstride = p.tail_slices;
+        gw = part[0].u1 - part[0].u0;
+        if (nparts == 2) {
+          next_block = rb + 1;
+          next_units = part[1].u1;
+        }
+      }
     } else {
       rb = blockIdx.x + it * (int)gridDim.x;
       if (it > 0 && (!p.block_stride || rb >= p.nrb)) break;
@@ -1664,7 +1686,7 @@ __global__ __launch_bounds__(64 * eval_waves(R, K)) void eval_kernel(EvalArgs p)
         gy = blockIdx.y;
       }
     }
-    eval_block<T, R, K, MODE, XLDS>(p, smem, rb, gy, gslice, gstride);
+    eval_block<T, R, K, MODE, XLDS>(p, smem, rb, gy, gslice, gstride, gw);
     if (!p.persistent && !p.block_stride) break;
     __syncthreads();  // every wave is done with this block's LDS (and has read `claimed`)
   }

@@ -2402,17 +2402,43 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
       HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     const int nmain = L.nrb - probe_blocks;
-    const int wgs = std::max(1, std::min(nmain, ctx->num_cu));
-    // SRHIP_TAIL_SLICES = S > 1: the row blocks past the last whole round of workgroups are claimed
-    // as S interleaved population slices each (C2's 485 blocks on 256 workgroups leave 229 for a
-    // second round that idles 27 CUs for a block).  Default 1 (whole blocks): every slice restages
-    // the block and re-derives its columns, and that costs more than the idle CUs (C2, same box:
-    // S = 1 1.215 ms, 8 1.250, 16 1.278)
-    const int slices_env = env_int("SRHIP_TAIL_SLICES", 1);
-    const int slices = std::max(1, std::min(slices_env, 64));
-    a.tail_slices = slices;
-    a.tail_blocks = slices > 1 && nmain > wgs && nl >= 16 * slices ? nmain % wgs : 0;
-    J.expect_items = nmain - a.tail_blocks + a.tail_blocks * slices;
+    // The last round in equal shares (srhip_tail_shares.h).  Whole blocks on wgs workgroups leave the
+    // Lb = nmain % wgs blocks past the last whole round to Lb workgroups while the others idle for a
+    // block: C2's 485 blocks on 256 workgroups last 2.0 block times for 1.894 of work, and 49 blocks
+    // (100k rows) run on 49 of 256 CUs.  Claiming those blocks as S population slices each, one by
+    // one, cannot help: the round then lasts ceil(Lb S / wgs) / S block times -- C2: 8/8 at S = 8,
+    // 15/16 at S = 16 -- and every slice restages its block and re-derives its columns (C2, same box:
+    // whole blocks 1.215 ms, S = 8 1.250, 16 1.278).  Instead the Lb S units are dealt to the
+    // workgroups as nshares contiguous ranges of near-equal length, one claim each: a share stages at
+    // most two blocks however many units it holds, and at S = 128 C2's round lasts 115/128 block times
+    // (units are an index mapping, not a staging: the finest S of the measured 32 / 64 / 128 is as fast
+    // or faster at 300k and 1M rows, profiles/r07_tail_shares.txt).
+    // A launch of fewer blocks than workgroups is all last round (nfull = 0) and fills the device.
+    //   SRHIP_TAIL_BALANCE=0: whole blocks; SRHIP_TAIL_SLICES=S > 1: units per block (default
+    //   TAIL_UNITS, at most 128); SRHIP_TAIL_SHARE_ROUNDS=2: 2 wgs shares; SRHIP_PERSISTENT_WGS=n
+    //   (tests): at most n workgroups.  Read per launch.
+    // Gate: the average share holds a tree per wave of a workgroup, nl Lb >= waves nshares -- below
+    // that a share's waves idle and its staging buys nothing; then whole blocks, as before.
+    constexpr int TAIL_UNITS = 128;
+    const int wgs_cap = std::max(1, std::min(env_int("SRHIP_PERSISTENT_WGS", ctx->num_cu), ctx->num_cu));
+    const int units_env = env_int("SRHIP_TAIL_SLICES", 0);
+    const int units = units_env > 1 ? std::min(units_env, 128) : TAIL_UNITS;
+    int wgs = std::max(1, std::min(nmain, wgs_cap));
+    a.tail_slices = 1;
+    a.tail_blocks = 0;
+    a.tail_shares = 0;
+    if (env_int("SRHIP_TAIL_BALANCE", 1) != 0 && nmain % wgs_cap != 0) {
+      const int lb = nmain % wgs_cap;
+      const int nshares = wgs_cap * (env_int("SRHIP_TAIL_SHARE_ROUNDS", 1) == 2 ? 2 : 1);
+      if ((int64_t)nl * lb >= (int64_t)eval_waves(R, K) * nshares &&
+          (int64_t)lb * units * nshares < ((int64_t)1 << 31)) {
+        wgs = wgs_cap;
+        a.tail_slices = units;
+        a.tail_blocks = lb;
+        a.tail_shares = nshares;
+      }
+    }
+    J.expect_items = nmain - a.tail_blocks + a.tail_shares;
     HIP_TRY(launch_eval(dtype, a, R, K, mode, true, dim3(wgs, 1), L.lds, ctx->stream));
   } else {
     HIP_TRY(launch_eval(dtype, a, R, K, mode, L.xlds, grid, L.lds, ctx->stream));
@@ -3589,6 +3615,20 @@ int srhip_code_cache_stats(int64_t* hits, int64_t* misses, int64_t* inserts) {
   if (misses) *misses = g_cache_misses.load();
   if (inserts) *inserts = g_cache_inserts.load();
   return SRHIP_OK;
+}
+
+int srhip_tail_share_parts(int32_t blocks, int32_t units, int32_t nshares, int32_t share, int32_t* out) {
+  if (!out || blocks < 1 || units < 1 || nshares < blocks || share < 0 || share >= nshares ||
+      (int64_t)blocks * units * nshares >= ((int64_t)1 << 31))
+    return -1;
+  TailPart part[2];
+  const int n = tail_share_parts(blocks, units, nshares, share, part);
+  for (int i = 0; i < n; ++i) {
+    out[3 * i] = part[i].block;
+    out[3 * i + 1] = part[i].u0;
+    out[3 * i + 2] = part[i].u1;
+  }
+  return n;
 }
 
 int srhip_last_work(const srhip_ctx* ctx, int64_t* out) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "srhip_isa.h"
+#include "srhip_tail_shares.h"
 
 namespace srhip {
 
@@ -95,8 +96,9 @@ struct EvalArgs {
   // block0 .. nrb-1 from *block_ctr (zeroed before the launch)
   int32_t persistent;
   int32_t block0;
-  int32_t tail_blocks;      // the last tail_blocks row blocks are claimed as tail_slices population slices each
-  int32_t tail_slices;
+  int32_t tail_blocks;      // the last tail_blocks row blocks, tail_slices units each, are claimed as
+  int32_t tail_slices;      // tail_shares equal shares of their units (srhip_tail_shares.h); 0 blocks:
+  int32_t tail_shares;      // every block is claimed whole
   int32_t grid_interleave;  // grid launches: workgroup (x, y) takes order slots y, y + grid.y, ... (group_off unused)
   int32_t tile_claims;      // a wave claims one (tree, tile) at a time (R = 16 probe; slab_chk / slab_rows zeroed first)
   int32_t block_stride;     // grid launches: workgroup x takes row blocks x, x + grid.x, ... (< nrb)

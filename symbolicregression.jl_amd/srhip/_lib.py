@@ -136,6 +136,7 @@ SIGNATURES = {
                                            ctypes.POINTER(_i32)]),
     "srhip_program_derived": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), _vp, _i32]),
     "srhip_code_cache_stats": (ctypes.c_int, [ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "srhip_tail_share_parts": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp]),
 }
 
 _lib = None
