@@ -10,9 +10,16 @@
  * differences (Optim with only f, FiniteDiff central steps); libsrhip differentiates exactly (dual
  * numbers), so the optimiser's state machine is checked against a restatement that differentiates
  * exactly too, and the finite-difference restatement stays the reference-deviation check.
- * Float64 trees; + - * / pow, and the unary operators with a derivative below (others: NaN).
+ * Every operator with a derivative has its analytic rule below, restated from the definitions (the same
+ * formulas the device's srhip_grad_impl.h states, written independently of it and pinned against
+ * tests/golden/derivative_rules.npz, a 40-digit table); the conventions at the kinks are the device's
+ * (DESIGN.md "Derivative conventions"): abs'(0) = relu'(0) = 0, max / min at a tie (0, 1), cond at
+ * a = 0 a second partial of 0, d(a ^ b)/db = 0 for a <= 0.  gamma has no rule: NaN.
  */
 #define GRAD_MAXC 64
+#define GRAD_LN2 0.69314718055994530942
+#define GRAD_LN10 2.30258509299404568402
+#define GRAD_2_SQRTPI 1.12837916709551257390 /* 2 / sqrt(pi) */
 
 typedef struct {
   const srhip_node* nd;
@@ -45,14 +52,32 @@ static double grad_node(const GradCtx* c, int64_t i, double* t) {
       case SRHIP_OP_SQUARE: df = 2.0 * x; break;
       case SRHIP_OP_CUBE: df = 3.0 * x * x; break;
       case SRHIP_OP_ABS: df = x > 0.0 ? 1.0 : (x < 0.0 ? -1.0 : 0.0); break;
+      case SRHIP_OP_RELU: df = x > 0.0 ? 1.0 : 0.0; break;
+      case SRHIP_OP_SIGN: case SRHIP_OP_ROUND: case SRHIP_OP_FLOOR: case SRHIP_OP_CEIL: df = 0.0; break;
       case SRHIP_OP_COS: df = -srm_sin(x); break;
       case SRHIP_OP_SIN: df = srm_cos(x); break;
       case SRHIP_OP_TAN: df = 1.0 + f * f; break;
       case SRHIP_OP_EXP: df = f; break;
       case SRHIP_OP_LOG: df = 1.0 / x; break;
+      case SRHIP_OP_LOG2: df = 1.0 / (x * GRAD_LN2); break;
+      case SRHIP_OP_LOG10: df = 1.0 / (x * GRAD_LN10); break;
+      case SRHIP_OP_LOG1P: df = 1.0 / (1.0 + x); break;
       case SRHIP_OP_SQRT: df = 0.5 / f; break;
+      case SRHIP_OP_ACOSH: df = 1.0 / sqrt(x * x - 1.0); break;
+      case SRHIP_OP_ATANH_CLIP: { const double u = julia_modf64(x + 1.0, 2.0) - 1.0; df = 1.0 / (1.0 - u * u); break; }
+      case SRHIP_OP_SINH: df = cosh(x); break;
+      case SRHIP_OP_COSH: df = sinh(x); break;
       case SRHIP_OP_TANH: df = 1.0 - f * f; break;
-      default: df = NAN; break;
+      case SRHIP_OP_ASIN: df = 1.0 / sqrt(1.0 - x * x); break;
+      case SRHIP_OP_ACOS: df = -1.0 / sqrt(1.0 - x * x); break;
+      case SRHIP_OP_ATAN: df = 1.0 / (1.0 + x * x); break;
+      case SRHIP_OP_ASINH: df = 1.0 / sqrt(x * x + 1.0); break;
+      case SRHIP_OP_ERF: df = GRAD_2_SQRTPI * srm_exp(-x * x); break;
+      case SRHIP_OP_ERFC: df = -GRAD_2_SQRTPI * srm_exp(-x * x); break;
+      case SRHIP_OP_EXP2: df = f * GRAD_LN2; break;
+      case SRHIP_OP_EXPM1: df = f + 1.0; break;
+      case SRHIP_OP_CBRT: df = 1.0 / (3.0 * f * f); break;
+      default: df = NAN; break; /* gamma: no digamma, no gradient */
     }
     for (int k = 0; k < c->nc; ++k) t[k] = df * t[k];
     return f;
@@ -69,6 +94,12 @@ static double grad_node(const GradCtx* c, int64_t i, double* t) {
     case SRHIP_OP_MUL: fa = b; fb = a; break;
     case SRHIP_OP_DIV: { const double ib = 1.0 / b; fa = ib; fb = -f * ib; break; }
     case SRHIP_OP_POW: fa = b * bin_f64(SRHIP_OP_POW, a, b - 1.0); fb = a > 0.0 ? f * srm_log(a) : 0.0; break;
+    case SRHIP_OP_MOD: fa = 1.0; fb = -floor(a / b); break;
+    case SRHIP_OP_ATAN2: { const double r = 1.0 / (a * a + b * b); fa = b * r; fb = -a * r; break; }
+    case SRHIP_OP_MAX: fa = a > b ? 1.0 : 0.0; fb = a > b ? 0.0 : 1.0; break; /* tie: (0, 1) */
+    case SRHIP_OP_MIN: fa = a < b ? 1.0 : 0.0; fb = a < b ? 0.0 : 1.0; break;
+    case SRHIP_OP_COND: fa = 0.0; fb = a > 0.0 ? 1.0 : 0.0; break;
+    case SRHIP_OP_GREATER: case SRHIP_OP_LOGICAL_OR: case SRHIP_OP_LOGICAL_AND: fa = 0.0; fb = 0.0; break;
     default: fa = NAN; fb = NAN; break;
   }
   for (int k = 0; k < c->nc; ++k) t[k] = fa * t[k] + fb * tr[k];
@@ -217,14 +248,32 @@ static float grad_node_f32(const GradCtx* c, const float* X32, int64_t i, float*
       case SRHIP_OP_SQUARE: df = 2.0f * x; break;
       case SRHIP_OP_CUBE: df = 3.0f * x * x; break;
       case SRHIP_OP_ABS: df = x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); break;
+      case SRHIP_OP_RELU: df = x > 0.0f ? 1.0f : 0.0f; break;
+      case SRHIP_OP_SIGN: case SRHIP_OP_ROUND: case SRHIP_OP_FLOOR: case SRHIP_OP_CEIL: df = 0.0f; break;
       case SRHIP_OP_COS: df = -srm_sinf(x); break;
       case SRHIP_OP_SIN: df = srm_cosf(x); break;
       case SRHIP_OP_TAN: df = 1.0f + f * f; break;
       case SRHIP_OP_EXP: df = f; break;
       case SRHIP_OP_LOG: df = 1.0f / x; break;
+      case SRHIP_OP_LOG2: df = 1.0f / (x * (float)GRAD_LN2); break;
+      case SRHIP_OP_LOG10: df = 1.0f / (x * (float)GRAD_LN10); break;
+      case SRHIP_OP_LOG1P: df = 1.0f / (1.0f + x); break;
       case SRHIP_OP_SQRT: df = 0.5f / f; break;
+      case SRHIP_OP_ACOSH: df = 1.0f / sqrtf(x * x - 1.0f); break;
+      case SRHIP_OP_ATANH_CLIP: { const float u = julia_modf32(x + 1.0f, 2.0f) - 1.0f; df = 1.0f / (1.0f - u * u); break; }
+      case SRHIP_OP_SINH: df = W1(cosh, x); break;
+      case SRHIP_OP_COSH: df = W1(sinh, x); break;
       case SRHIP_OP_TANH: df = 1.0f - f * f; break;
-      default: df = NAN; break;
+      case SRHIP_OP_ASIN: df = 1.0f / sqrtf(1.0f - x * x); break;
+      case SRHIP_OP_ACOS: df = -1.0f / sqrtf(1.0f - x * x); break;
+      case SRHIP_OP_ATAN: df = 1.0f / (1.0f + x * x); break;
+      case SRHIP_OP_ASINH: df = 1.0f / sqrtf(x * x + 1.0f); break;
+      case SRHIP_OP_ERF: df = (float)GRAD_2_SQRTPI * srm_expf(-x * x); break;
+      case SRHIP_OP_ERFC: df = -(float)GRAD_2_SQRTPI * srm_expf(-x * x); break;
+      case SRHIP_OP_EXP2: df = f * (float)GRAD_LN2; break;
+      case SRHIP_OP_EXPM1: df = f + 1.0f; break;
+      case SRHIP_OP_CBRT: df = 1.0f / (3.0f * f * f); break;
+      default: df = NAN; break; /* gamma: no digamma, no gradient */
     }
     for (int k = 0; k < c->nc; ++k) t[k] = df * t[k];
     return f;
@@ -240,6 +289,13 @@ static float grad_node_f32(const GradCtx* c, const float* X32, int64_t i, float*
     case SRHIP_OP_SUB: fa = 1.0f; fb = -1.0f; break;
     case SRHIP_OP_MUL: fa = b; fb = a; break;
     case SRHIP_OP_DIV: { const float ib = 1.0f / b; fa = ib; fb = -f * ib; break; }
+    case SRHIP_OP_POW: fa = b * bin_f32(SRHIP_OP_POW, a, b - 1.0f); fb = a > 0.0f ? f * srm_logf(a) : 0.0f; break;
+    case SRHIP_OP_MOD: fa = 1.0f; fb = -floorf(a / b); break;
+    case SRHIP_OP_ATAN2: { const float r = 1.0f / (a * a + b * b); fa = b * r; fb = -a * r; break; }
+    case SRHIP_OP_MAX: fa = a > b ? 1.0f : 0.0f; fb = a > b ? 0.0f : 1.0f; break; /* tie: (0, 1) */
+    case SRHIP_OP_MIN: fa = a < b ? 1.0f : 0.0f; fb = a < b ? 0.0f : 1.0f; break;
+    case SRHIP_OP_COND: fa = 0.0f; fb = a > 0.0f ? 1.0f : 0.0f; break;
+    case SRHIP_OP_GREATER: case SRHIP_OP_LOGICAL_OR: case SRHIP_OP_LOGICAL_AND: fa = 0.0f; fb = 0.0f; break;
     default: fa = NAN; fb = NAN; break;
   }
   for (int k = 0; k < c->nc; ++k) t[k] = fa * t[k] + fb * tr[k];
