@@ -46,7 +46,6 @@
 using namespace srhip;
 
 static bool env_flag(const char* name);
-static int env_int(const char* name, int dflt);
 
 // ---------------------------------------------------------------------------------------------
 // errors
@@ -1281,19 +1280,8 @@ bool spec_instantiate_t(srhip_program& P, int32_t slot, int32_t t, const double*
   // the tree's nodes at the constants c (get_constants order = pre-order over constant leaves)
   const int64_t b = P.offsets[t], e = P.offsets[t + 1];
   std::vector<srhip_node> nd(P.nodes.begin() + b, P.nodes.begin() + e);
-  struct Rec {
-    static void set(std::vector<srhip_node>& v, int64_t i, const double*& c) {
-      srhip_node& n = v[(size_t)i];
-      if (n.degree == 0) {
-        if (n.constant) n.val = *c++;
-        return;
-      }
-      set(v, n.l, c);
-      if (n.degree == 2) set(v, n.r, c);
-    }
-  };
   const double* cp = c;
-  Rec::set(nd, 0, cp);
+  set_consts(nd.data(), 0, cp);
   TreeCompiler<T> tc(nd.data(), e - b, P, 0, true);
   if (!P.gspec_ok[t]) {  // the code's shape is not known to be value-independent: compile it
     std::vector<Ins> scratch;
@@ -1349,17 +1337,6 @@ void grad_snapshot(srhip_program& P) {
 // gradient program was compiled with.  A tree's code depends on its own nodes only and is
 // position-independent, so an unchanged length means the new code drops into the old slot; any
 // other outcome (length change, no snapshot) returns patched = false and the caller recompiles all.
-// a tree's constant values in get_constants order (pre-order over constant leaves)
-void gather_consts_preorder(const srhip_node* nd, int64_t i, std::vector<double>& out) {
-  const srhip_node& n = nd[i];
-  if (n.degree == 0) {
-    if (n.constant) out.push_back(n.val);
-    return;
-  }
-  gather_consts_preorder(nd, n.l, out);
-  if (n.degree == 2) gather_consts_preorder(nd, n.r, out);
-}
-
 template <typename T>
 int patch_grad_t(srhip_program& P, bool& patched, int64_t& lo, int64_t& hi) {
   patched = false;
@@ -1395,8 +1372,9 @@ int patch_grad_t(srhip_program& P, bool& patched, int64_t& lo, int64_t& hi) {
     if ((size_t)t < P.gspec_ok.size() && P.gspec_ok[t]) {
       // the code is the full compile's with new constant immediates; the did_succeed metadata is
       // recomputed from the new values (constant leaves' finiteness, constant subtrees folded)
-      cvals.clear();
-      gather_consts_preorder(P.nodes.data() + b, 0, cvals);
+      cvals.resize(P.info[t].nconst);
+      double* cv = cvals.data();
+      get_consts(P.nodes.data() + b, 0, cv);
       TreeInfo meta;
       TreeCompiler<T>(P.nodes.data() + b, e - b, P, 0, true).static_info(meta);
       TreeInfo& cur = P.ginfo[t];
@@ -1448,9 +1426,6 @@ int patch_grad_t(srhip_program& P, bool& patched, int64_t& lo, int64_t& hi) {
 }  // namespace
 
 thread_local double srhip::g_patch_scan_s = 0.0, srhip::g_patch_copy_s = 0.0;
-static double host_now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 bool srhip::spec_instantiate(srhip_program& P, int32_t slot, int32_t t, const double* c, bool* static_fail,
                              int64_t& lo, int64_t& hi) {
   switch (P.dtype) {
@@ -1493,19 +1468,19 @@ int srhip::compile_grad_program(srhip_program& P) {
   int rc;
   bool patched = false;
   int64_t lo = 0, hi = -1;  // patched instruction range
-  const double t_patch0 = host_now_s();
+  const double t_patch0 = now_s();
   if (!no_patch && same_form && P.ctx && P.d_gcode.p) {  // a previous full compile is on the device
     switch (P.dtype) {
       case SRHIP_F32: rc = patch_grad_t<float>(P, patched, lo, hi); break;
       case SRHIP_F64: rc = patch_grad_t<double>(P, patched, lo, hi); break;
       default: rc = SRHIP_OK; break;
     }
-    g_patch_scan_s += host_now_s() - t_patch0;
+    g_patch_scan_s += now_s() - t_patch0;
     if (rc) return rc;
   }
   P.ghint.clear();
   if (patched) {  // the device copy differs only in [lo, hi); the snapshot was updated by the patch
-    const double t_copy0 = host_now_s();
+    const double t_copy0 = now_s();
     HIP_TRY(hipSetDevice(P.ctx->device));
     if (hi > lo) {  // through pinned staging: a pageable source makes the runtime stage it synchronously
       const size_t nb = (size_t)(hi - lo) * sizeof(Ins);
@@ -1515,7 +1490,7 @@ int srhip::compile_grad_program(srhip_program& P) {
     }
     // no synchronisation here: the gradient launch follows on the same stream, and eval_grad
     // synchronises before it returns, so the staging is not touched while this copy is in flight
-    g_patch_copy_s += host_now_s() - t_copy0;
+    g_patch_copy_s += now_s() - t_copy0;
     P.grad_ready = true;
     return SRHIP_OK;
   }
@@ -1769,7 +1744,6 @@ std::vector<int32_t> make_order(const srhip_program& P, const std::vector<int32_
 // data: sum of x * 2^-64), sums[2T + 2f + 1] = its non-finite count; sums[2T + 2F] = rows.  Every
 // entry combines across row shards by addition; chk[t] (the operator-output check statistic)
 // combines by max for Float32 (max |v|) and by addition for Float64 (sum of |v| 2^-512).
-static size_t sums_len(int32_t ntrees, int64_t nfeat) { return 2 * (size_t)ntrees + 2 * (size_t)nfeat + 1; }
 
 // Returns 0 ok, 1 fail, 2 undecided (needs the precise pass).
 static int decide_info(const TreeInfo& I, int dtype, int32_t T, int64_t nfeat, const double* sums, double chk) {
@@ -1952,10 +1926,6 @@ int srhip::check_eval_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_
 static bool env_flag(const char* name) {
   const char* e = env_get(name);
   return e && *e && *e != '0';
-}
-static int env_int(const char* name, int dflt) {
-  const char* e = env_get(name);
-  return e && *e ? atoi(e) : dflt;
 }
 
 // run_eval's device-decided precise pass: the reduction lists the trees whose overflow bound needs
@@ -3226,37 +3196,17 @@ int srhip_program_num_constants(const srhip_program* P, int32_t* out) {
   return SRHIP_OK;
 }
 
-static void set_consts_rec(std::vector<srhip_node>& nodes, int64_t base, int64_t i, const double*& c) {
-  srhip_node& n = nodes[base + i];
-  if (n.degree == 0) {
-    if (n.constant) n.val = *c++;
-    return;
-  }
-  set_consts_rec(nodes, base, n.l, c);
-  if (n.degree == 2) set_consts_rec(nodes, base, n.r, c);
-}
-
-static void get_consts_rec(const std::vector<srhip_node>& nodes, int64_t base, int64_t i, double*& c) {
-  const srhip_node& n = nodes[base + i];
-  if (n.degree == 0) {
-    if (n.constant) *c++ = n.val;
-    return;
-  }
-  get_consts_rec(nodes, base, n.l, c);
-  if (n.degree == 2) get_consts_rec(nodes, base, n.r, c);
-}
-
 int srhip_program_get_constants(const srhip_program* P, double* consts) {
   if (!P || (!consts && P->ntrees > 0)) return fail(SRHIP_ERR_INVALID, "null argument");
   double* c = consts;
-  for (int32_t t = 0; t < P->ntrees; ++t) get_consts_rec(P->nodes, P->offsets[t], 0, c);
+  for (int32_t t = 0; t < P->ntrees; ++t) get_consts(P->nodes.data() + P->offsets[t], 0, c);
   return SRHIP_OK;
 }
 
 int srhip_program_set_constants(srhip_program* P, const double* consts) {
   if (!P || (!consts && P->ntrees > 0)) return fail(SRHIP_ERR_INVALID, "null argument");
   const double* c = consts;
-  for (int32_t t = 0; t < P->ntrees; ++t) set_consts_rec(P->nodes, P->offsets[t], 0, c);
+  for (int32_t t = 0; t < P->ntrees; ++t) set_consts(P->nodes.data() + P->offsets[t], 0, c);
   {
     // new constants can change which trees fail statically (non-finite leaves): the next evaluation
     // plans its launch order again
@@ -3275,28 +3225,21 @@ int srhip_eval_loss(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program
   return run_eval(ctx, ds, prog, MODE_LOSS, loss, idx, nidx, out_loss, nullptr, out_ok);
 }
 
-// ---- srhip_eval_loss_rowsets: one row subset per tree, one launch (srhip_rowsets.hip) ----------------
-// Tree t of P alone on its set through the single-subset path (a one-tree program): the sets no wave
-// can stage, and the rare trees the fast bound leaves undecided (the precise pass lives there).
-static int rowset_single(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int32_t t, const srhip_loss* loss,
-                         const int64_t* rows, int64_t m, double* out_loss, uint8_t* out_ok) {
-  srhip_operators ops{(int32_t)P->binops.size(), (int32_t)P->unaops.size(), P->binops.data(), P->unaops.data()};
-  const int64_t offs[2] = {0, P->offsets[t + 1] - P->offsets[t]};
-  srhip_program* Q = nullptr;
-  int rc = srhip_program_create(ctx, P->dtype, P->nodes.data() + P->offsets[t], offs, 1, &ops, &Q);
-  if (rc) return rc;
-  rc = run_eval(ctx, ds, Q, MODE_LOSS, loss, rows, m, out_loss, nullptr, out_ok);
-  srhip_program_destroy(Q);
-  return rc;
+}  // extern "C"
+
+int srhip::subprogram(srhip_ctx* ctx, const srhip_program* P, const std::vector<int32_t>& trees, srhip_program** Q) {
+  const srhip_operators ops{(int32_t)P->binops.size(), (int32_t)P->unaops.size(), P->binops.data(), P->unaops.data()};
+  std::vector<srhip_node> nodes;
+  std::vector<int64_t> offs(1, 0);
+  for (int32_t t : trees) {
+    nodes.insert(nodes.end(), P->nodes.begin() + P->offsets[t], P->nodes.begin() + P->offsets[t + 1]);
+    offs.push_back((int64_t)nodes.size());
+  }
+  return srhip_program_create(ctx, P->dtype, nodes.data(), offs.data(), (int32_t)trees.size(), &ops, Q);
 }
 
-int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
-                            const int64_t* row_offsets, const int64_t* rows, double* out_loss, uint8_t* out_ok) {
-  if (!row_offsets || !rows || !out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
-  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
-  if (rc) return rc;
+int srhip::check_rowsets(const srhip_dataset* ds, int32_t nt, const int64_t* row_offsets, const int64_t* rows) {
   if (!ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
-  const int32_t nt = P->ntrees;
   if (row_offsets[0] != 0) return fail(SRHIP_ERR_INVALID, "row_offsets[0] must be 0");
   for (int32_t t = 0; t < nt; ++t) {
     if (row_offsets[t + 1] < row_offsets[t])
@@ -3308,6 +3251,32 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
         return fail(SRHIP_ERR_INVALID, "tree %d: rows[%lld] (position %lld of its set) = %lld out of range [0, %lld)", (int)t,
                     (long long)p, (long long)(p - row_offsets[t]), (long long)rows[p], (long long)ds->n);
   }
+  return SRHIP_OK;
+}
+
+extern "C" {
+
+// ---- srhip_eval_loss_rowsets: one row subset per tree, one launch (srhip_rowsets.hip) ----------------
+// Tree t of P alone on its set through the single-subset path (a one-tree program): the sets no wave
+// can stage, and the rare trees the fast bound leaves undecided (the precise pass lives there).
+static int rowset_single(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int32_t t, const srhip_loss* loss,
+                         const int64_t* rows, int64_t m, double* out_loss, uint8_t* out_ok) {
+  srhip_program* Q = nullptr;
+  int rc = subprogram(ctx, P, {t}, &Q);
+  if (rc) return rc;
+  rc = run_eval(ctx, ds, Q, MODE_LOSS, loss, rows, m, out_loss, nullptr, out_ok);
+  srhip_program_destroy(Q);
+  return rc;
+}
+
+int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
+                            const int64_t* row_offsets, const int64_t* rows, double* out_loss, uint8_t* out_ok) {
+  if (!row_offsets || !rows || !out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
+  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  const int32_t nt = P->ntrees;
+  rc = check_rowsets(ds, nt, row_offsets, rows);
+  if (rc) return rc;
   if (nt == 0) return SRHIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   const int dtype = P->dtype;
@@ -3418,7 +3387,6 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
   // every launched tree decided on its own record: its set's rows, feature statistics and +/- bound
   int64_t work[4] = {0, 0, 0, 0};
   std::vector<double> sums(sums_len(nt, nf), 0.0);
-  double* const tail = sums.data() + 2 * (size_t)nt;
   std::vector<int32_t> undecided;
   const bool fast = pdec && !env_flag("SRHIP_DECIDE_SLOW");
   for (int32_t t = 0; t < nt; ++t) {  // statically failing trees, and defaults
@@ -3430,11 +3398,7 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
     View v{};
     v.m = m;
     v.stats = fstat + (size_t)t * nf;
-    for (int64_t f = 0; f < nf; ++f) {
-      tail[2 * f] = dtype == SRHIP_I32 ? 0.0 : v.stats[f].sum;
-      tail[2 * f + 1] = dtype == SRHIP_I32 ? 0.0 : (double)v.stats[f].nonfinite;
-    }
-    tail[2 * nf] = (double)m;
+    fill_decide_inputs(sums.data(), nt, nf, dtype == SRHIP_I32 ? nullptr : v.stats, m);  // (Int32 data: zeros)
     double chk = 0.0;
     if (dtype == SRHIP_F32)
       chk = skip_bound_apply(((const float*)r_chk.data())[t], P->sbound.data() + 4 * (size_t)t, feature_bound(v, nf));

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <chrono>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -408,6 +409,52 @@ const char* env_get(const char* name);
 // next population beside the evaluation (fresh compile 0.59 -> 0.80 ms, pipelined population
 // 1.63 -> 1.95 ms), so blocking is the default.
 int stream_wait(srhip_ctx* ctx);
+// integer knob through the environment cache (read per call: tests flip it within one process)
+inline int env_int(const char* name, int dflt) {
+  const char* e = env_get(name);
+  return e && *e ? atoi(e) : dflt;
+}
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// ---- rules shared by the evaluation, gradient and optimiser entry points --------------------------
+// A tree's constants in get_constants order (pre-order over the constant leaves of the tree rooted at
+// nd[i], a shared subtree once per use; TreeInfo::nconst of them): read to *out++ / written from *c++.
+inline void get_consts(const srhip_node* nd, int64_t i, double*& out) {
+  const srhip_node& n = nd[i];
+  if (n.degree == 0) {
+    if (n.constant) *out++ = n.val;
+    return;
+  }
+  get_consts(nd, n.l, out);
+  if (n.degree == 2) get_consts(nd, n.r, out);
+}
+inline void set_consts(srhip_node* nd, int64_t i, const double*& c) {
+  srhip_node& n = nd[i];
+  if (n.degree == 0) {
+    if (n.constant) n.val = *c++;
+    return;
+  }
+  set_consts(nd, n.l, c);
+  if (n.degree == 2) set_consts(nd, n.r, c);
+}
+// The listed trees of P, at their current constants, as a program of its own on ctx.
+int subprogram(srhip_ctx* ctx, const srhip_program* P, const std::vector<int32_t>& trees, srhip_program** Q);
+// The row-set entry points' conventions and error texts: offsets from 0, no empty set, rows in range.
+int check_rowsets(const srhip_dataset* ds, int32_t nt, const int64_t* row_offsets, const int64_t* rows);
+// The partials layout decide_tree reads (srhip_host.cpp "the did_succeed decision"): its length, and the
+// decision inputs of one view or row set written into it -- (sum, non-finite count) per feature (zeros
+// without stats: Int32 data), then the row count.  The per-tree entries in front are left alone.
+inline size_t sums_len(int32_t ntrees, int64_t nfeat) { return 2 * (size_t)ntrees + 2 * (size_t)nfeat + 1; }
+inline void fill_decide_inputs(double* sums, int32_t ntrees, int64_t nfeat, const FeatStat* stats, int64_t rows) {
+  double* const tail = sums + 2 * (size_t)ntrees;
+  for (int64_t f = 0; f < nfeat; ++f) {
+    tail[2 * f] = stats ? stats[f].sum : 0.0;
+    tail[2 * f + 1] = stats ? (double)stats[f].nonfinite : 0.0;
+  }
+  tail[2 * nfeat] = (double)rows;
+}
 int run_eval_sharded(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
                      const int64_t* idx, int64_t nidx, const ShardIO& io, double* out_loss, uint8_t* out_ok);
 

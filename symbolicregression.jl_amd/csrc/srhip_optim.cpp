@@ -16,8 +16,9 @@
 //   of a second difference of losses -- parity is on the optimised loss, SURVEY.md 8(a) A13.
 // srhip_eval_loss_grad_rowsets / srhip_optimize_constants_rowsets: the same two with one row subset per
 //   tree (the batching mode's batch_sample per member, src/ConstantOptimization.jl:14-17): the optimiser's
-//   evaluation primitive runs every item on its tree's own set (eval_grad_items_rowsets over
-//   srhip_grad_rowsets.hip), everything above it is the one code path.
+//   evaluation primitive (eval_grad_items) runs every item on its tree's own set (RowsetBackend over
+//   srhip_grad_rowsets.hip, in place of ViewBackend over srhip_grad.hip), everything above it is the
+//   one code path.
 #include <algorithm>
 #include <numeric>
 #include <chrono>
@@ -63,31 +64,14 @@ std::vector<int64_t> const_offsets(const srhip_program& P) {
   return c;
 }
 
-void get_consts_rec(const srhip_node* nd, int64_t i, std::vector<double>& out) {
-  const srhip_node& n = nd[i];
-  if (n.degree == 0) {
-    if (n.constant) out.push_back(n.val);
-    return;
-  }
-  get_consts_rec(nd, n.l, out);
-  if (n.degree == 2) get_consts_rec(nd, n.r, out);
-}
-void set_consts_rec(srhip_node* nd, int64_t i, const double*& c) {
-  srhip_node& n = nd[i];
-  if (n.degree == 0) {
-    if (n.constant) n.val = *c++;
-    return;
-  }
-  set_consts_rec(nd, n.l, c);
-  if (n.degree == 2) set_consts_rec(nd, n.r, c);
-}
 std::vector<double> get_all_consts(const srhip_program& P) {
-  std::vector<double> out;
-  for (int32_t t = 0; t < P.ntrees; ++t) get_consts_rec(P.nodes.data() + P.offsets[t], 0, out);
+  std::vector<double> out(const_offsets(P).back());
+  double* c = out.data();
+  for (int32_t t = 0; t < P.ntrees; ++t) get_consts(P.nodes.data() + P.offsets[t], 0, c);
   return out;
 }
 void set_all_consts(srhip_program& P, const double* c) {
-  for (int32_t t = 0; t < P.ntrees; ++t) set_consts_rec(P.nodes.data() + P.offsets[t], 0, c);
+  for (int32_t t = 0; t < P.ntrees; ++t) set_consts(P.nodes.data() + P.offsets[t], 0, c);
   P.grad_ready = false;
   P.ghint.clear();  // every tree may have changed
 }
@@ -106,14 +90,6 @@ static thread_local int64_t g_spec_launched = 0, g_spec_used = 0;  // speculativ
 // (SRHIP_OPTIM_TIMING=2) evaluated items by pass (0 gradient, 1 value-only) and launch size (items
 // <= 64 / > 64): [pass][big][all, non-finite f]
 static thread_local int64_t g_items[2][2][2] = {};
-// integer knob through the environment cache (read per call: tests flip it within one process)
-static int env_int_opt(const char* name, int dflt) {
-  const char* e = env_get(name);
-  return e && *e ? atoi(e) : dflt;
-}
-static double now_s() {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 // One gradient evaluation of the launch: program slot `slot` (a tree, or a speculative slot holding
 // tree `tree` at other constants) -> f (+Inf where did_succeed fails), g[0 .. nconst of tree), ok.
 struct GradItem {
@@ -134,13 +110,13 @@ static int derived_view(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* 
   P->g_want_derived = false;
   const char* e = env_get("SRHIP_GRAD_DERIVED");
   if (e && *e == '0') return SRHIP_OK;
-  if (v.m < env_int_opt("SRHIP_GRAD_DERIVED_MIN_ROWS", 8192)) return SRHIP_OK;
+  if (v.m < env_int("SRHIP_GRAD_DERIVED_MIN_ROWS", 8192)) return SRHIP_OK;
   grad_derived_spec(*P);
   const int nd = (int)P->gdspec.size();
   if (nd == 0 || P->gdbase <= 0) return SRHIP_OK;
   const size_t es = P->dtype == SRHIP_F64 ? 8 : 4;
   const size_t bytes = (size_t)(P->gdbase + 2 * nd) * v.ld * es;
-  if (bytes > ((size_t)env_int_opt("SRHIP_GRAD_DERIVED_MAX_MB", 256) << 20)) return SRHIP_OK;  // (a copy per call)
+  if (bytes > ((size_t)env_int("SRHIP_GRAD_DERIVED_MAX_MB", 256) << 20)) return SRHIP_OK;  // (a copy per call)
   // a view of the whole dataset (not a gathered batch) with the same spec as the last build: reused
   const bool whole = v.X == ds->X.p;
   const bool same = whole && ctx->g_xd.p && ctx->g_xd_serial == ds->serial && ctx->g_xd_ld == v.ld &&
@@ -172,7 +148,7 @@ static int derived_view(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* 
 // The row-set batch of one call (srhip_eval_loss_grad_rowsets / srhip_optimize_constants_rowsets): every
 // tree's own row subset, gathered once into a packed device buffer, with the per-set statistics the
 // decisions need.  Where a batch is given it replaces the View: item (slot, tree) is evaluated on tree's
-// set by grad_rowsets_kernel (eval_grad_items_rowsets) instead of on the view's rows.
+// set by grad_rowsets_kernel (RowsetBackend) instead of on the view's rows.
 struct RowsetBatch {
   const int64_t* row_off = nullptr;  // the caller's [ntrees + 1] offsets and row indices (validated)
   const int64_t* rows = nullptr;
@@ -184,9 +160,347 @@ struct RowsetBatch {
   const int64_t* d_set_off = nullptr;
   const int32_t* d_set_m = nullptr;
 };
+// One chunk of a launch, on the host: program slot, first constant, the item it reports to and that
+// item's tree (which names the row set where there is one).  A backend flattens it to its device list.
+struct Chunk {
+  int32_t slot, c0, item, tree;
+};
+// The two passes of an evaluation (gradient chunks of kt tangents, then value-only chunks: kt = 0)
+struct GradPass {
+  int kt;
+  std::vector<Chunk> chunks;    // in launch order once the backend has prepared the pass
+  const double* red = nullptr;  // the reduced records, (kt + 2) doubles per chunk by position (pinned staging)
+};
+// eval_grad_items' backends supply what differs between "every item on the view's rows" and "every item on
+// its tree's own row set":
+//   prepare(pass)           launch order of both passes' chunks, device buffers sized for both before the
+//                           first launch (no reallocation under a queued kernel)
+//   launch(pi, ps, ev0)     the pass's chunk list and kernels on the stream, its records written to
+//                           ctx->h_gred[pi]; ev0 (nullable) recorded in front of the kernels
+//   wsum(it)                the weight sum the item's records are divided by
+//   decide_inputs(it)       the partials-layout array decide_tree reads for the item
+//   settle(items, und, ok)  the precise pass for the undecided items `und`: ok[u] for items[und[u]]
+
+// Every item on the view's rows (srhip_grad.hip): row blocks x chunk groups, reduced by a second kernel.
+struct ViewBackend {
+  srhip_ctx* ctx;
+  const srhip_dataset* ds;
+  srhip_program* P;
+  const srhip_loss* loss;
+  const View& v;
+  LaunchPlan L[2] = {};
+  std::vector<double> sums;  // decision inputs: only the feature statistics and the row count are read
+
+  int prepare(GradPass (&pass)[2]) {
+    sums.assign(sums_len(P->ntrees, ds->nfeat), 0.0);
+    fill_decide_inputs(sums.data(), P->ntrees, ds->nfeat, v.stats, v.m);
+    size_t slab_n = 0, red_n = 0, chunk_n = 0;
+    for (int pi = 0; pi < 2; ++pi) {
+      GradPass& ps = pass[pi];
+      const int nch = (int)ps.chunks.size();
+      if (nch == 0) continue;
+      L[pi] = grad_plan(ctx, v.m, nch);
+      // launch order: descending estimated cost, dealt round-robin over the tree groups (each group's
+      // range stays contiguous), so every group gets the same cost mix and its waves -- which claim
+      // chunks dynamically -- start with the longest ones.  Records are read back by position.
+      if (nch > 1) {
+        std::vector<int32_t> by(nch);
+        std::iota(by.begin(), by.end(), 0);
+        std::stable_sort(by.begin(), by.end(), [&](int32_t x, int32_t y) {
+          return P->ginfo[ps.chunks[x].slot].cost > P->ginfo[ps.chunks[y].slot].cost;
+        });
+        const int G = L[pi].groups, tpg = L[pi].tpg;
+        std::vector<int32_t> fill(G, 0);
+        std::vector<Chunk> dealt(nch);
+        int g = 0;
+        for (int32_t k : by) {
+          while (fill[g] >= std::min(tpg, nch - g * tpg)) g = (g + 1) % G;
+          dealt[g * tpg + fill[g]++] = ps.chunks[k];
+          g = (g + 1) % G;
+        }
+        ps.chunks.swap(dealt);
+      }
+      slab_n = std::max(slab_n, (size_t)nch * L[pi].nrb * (ps.kt + 2));
+      red_n = std::max(red_n, (size_t)nch * (ps.kt + 2));
+      chunk_n = std::max(chunk_n, (size_t)2 * nch);
+    }
+    HIP_TRY(ctx->g_chunks.ensure(chunk_n * sizeof(int32_t)));
+    HIP_TRY(ctx->g_slab.ensure(slab_n * sizeof(double)));
+    HIP_TRY(ctx->g_red.ensure(red_n * sizeof(double)));
+    return SRHIP_OK;
+  }
+
+  int launch(int pi, const GradPass& ps, hipEvent_t ev0) {
+    const int dtype = P->dtype;
+    const bool weighted = ds->weighted;
+    const int nch = (int)ps.chunks.size();
+    const LaunchPlan& Lp = L[pi];
+    const int K = P->gkmax <= 2 ? 2 : (P->gkmax <= 4 ? 4 : 8);  // stack slots of the kernel variant
+    GradArgs a{};
+    // SRHIP_GRAD_INLINE_MAX (0: always copy the list), read per pass through the environment cache
+    // so a test can compare both forms in one process
+    const bool inl = nch <= std::max(0, std::min(env_int("SRHIP_GRAD_INLINE_MAX", GRAD_INLINE), GRAD_INLINE));
+    // the device list, (slot, c0) per chunk: in the kernel arguments, or through pinned staging (a pageable
+    // source makes the runtime stage the copy through its own buffer, synchronously); stream order: the
+    // copy follows the previous pass's kernel, which has read its chunk list
+    const size_t list_bytes = (size_t)2 * nch * sizeof(int32_t);
+    if (!inl) HIP_TRY(ctx->h_gchunks[pi].ensure(list_bytes));
+    int32_t* const list = inl ? a.inl : (int32_t*)ctx->h_gchunks[pi].p;
+    for (int c = 0; c < nch; ++c) {
+      list[2 * c] = ps.chunks[c].slot;
+      list[2 * c + 1] = ps.chunks[c].c0;
+    }
+    if (!inl) HIP_TRY(hipMemcpyAsync(ctx->g_chunks.p, list, list_bytes, hipMemcpyHostToDevice, ctx->stream));
+    a.code = (const Ins*)P->d_gcode.p;
+    a.prog_off = (const int32_t*)P->d_goff.p;
+    a.chunks = inl ? nullptr : (const int32_t*)ctx->g_chunks.p;
+    a.X = v.X;
+    a.y = v.y;
+    a.w = weighted ? v.w : nullptr;
+    a.slab = (double*)ctx->g_slab.p;
+    a.ld = v.ld;
+    a.nvalid = v.m;
+    a.nchunks = nch;
+    a.nfeat = v.nfeat_x >= 0 ? v.nfeat_x : (int32_t)ds->nfeat;
+    a.gd_nd = v.nd_x;
+    a.rb_rows = Lp.rb_rows;
+    a.nrb = Lp.nrb;
+    a.chunks_per_group = Lp.tpg;
+    a.loss_kind = loss->kind;
+    a.loss_p0 = loss->p0;
+    a.weighted = weighted ? 1 : 0;
+    a.max_steps = P->gmax_len;
+    if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));  // srhip_last_kernel_ms: the gradient kernels
+    // value-only screening (SRHIP_GRAD_SCREEN = the fewest value-only chunks screened; default 0 =
+    // off): row block 0 of every chunk first, in a launch of its own, then the other blocks, where a
+    // chunk whose block-0 check statistic is already non-finite is skipped.  Records of evaluated
+    // blocks are the same computation as in one launch, so losses and decisions are bit-identical
+    // (test_value_only_screening_is_exact).  C4 (~40 % of its trial points overflow), same box:
+    // off 173.6-177.9 ms, every pass 190-193, passes of >= 16 chunks 176.8-179.6 -- the extra launch
+    // costs what the skipped blocks save at 100k rows.
+    const int screen_min = env_int("SRHIP_GRAD_SCREEN", 0);
+    if (ps.kt == 0 && screen_min > 0 && nch >= screen_min && Lp.nrb > 1) {
+      GradArgs sa = a;
+      const int tpg_s = 2 * GRAD_WAVES;
+      sa.chunks_per_group = tpg_s;
+      HIP_TRY(launch_grad(dtype, K, 0, sa, dim3(1, (nch + tpg_s - 1) / tpg_s), ctx->stream));
+      a.block0 = 1;
+      a.screened = 1;
+      HIP_TRY(launch_grad(dtype, K, 0, a, dim3(Lp.nrb - 1, Lp.groups), ctx->stream));
+    } else {
+      HIP_TRY(launch_grad(dtype, K, ps.kt, a, dim3(Lp.nrb, Lp.groups), ctx->stream));
+    }
+    // the reduction writes the records straight into coherent pinned host memory (no copy on the stream)
+    HIP_TRY(launch_grad_reduce(dtype, ps.kt, (const double*)ctx->g_slab.p, Lp.nrb, nch, (double*)ctx->h_gred[pi].p,
+                               ctx->stream));
+    return SRHIP_OK;
+  }
+
+  double wsum(const GradItem&) const { return ds->weighted ? v.sum_w : (double)v.m; }
+  const double* decide_inputs(const GradItem&) { return sums.data(); }
+
+  // near-overflow sums: the exact per-operator-node pass on the gradient program decides, so the
+  // objective is eval_loss's (L(Inf) exactly where did_succeed fails); one batched pass over the view
+  int settle(const std::vector<GradItem>& items, const std::vector<int32_t>& und, uint8_t* ok) {
+    std::vector<int32_t> slots;
+    for (int32_t ui : und) slots.push_back(items[ui].slot);
+    return precise_decide(ctx, ds, P, v, slots.data(), (int32_t)slots.size(), true, ok);
+  }
+};
+
+// Every item on its tree's own row set (srhip_grad_rowsets.hip).  One single-wave workgroup per chunk
+// (slot, c0, set); the waves write the final (kt + 2) records straight into the pinned staging, so a pass
+// is one launch.  Each item is decided on its own set's statistics (feature sums, non-finite counts, rows,
+// weight sum); an undecided item (a near-overflow sum) is settled by the precise pass over a view gathered
+// from its set.
+struct RowsetBackend {
+  srhip_ctx* ctx;
+  const srhip_dataset* ds;
+  srhip_program* P;
+  const srhip_loss* loss;
+  const RowsetBatch& rb;
+  int max_ld[2] = {0, 0};
+  std::vector<double> sums;
+
+  int prepare(GradPass (&pass)[2]) {
+    sums.assign(sums_len(P->ntrees, ds->nfeat), 0.0);
+    size_t chunk_n = 0;
+    for (int pi = 0; pi < 2; ++pi) {
+      GradPass& ps = pass[pi];
+      for (const Chunk& c : ps.chunks) {
+        if (!rb.staged[c.tree]) return fail(SRHIP_ERR_INVALID, "tree %d: its row set is not staged", (int)c.tree);
+        max_ld[pi] = std::max(max_ld[pi], (rb.m[c.tree] + GRAD_ROWSET_RB - 1) / GRAD_ROWSET_RB * GRAD_ROWSET_RB);
+      }
+      // launch order: descending set length x tree cost
+      auto weight = [&](const Chunk& c) { return (double)rb.m[c.tree] * P->ginfo[c.slot].cost; };
+      std::stable_sort(ps.chunks.begin(), ps.chunks.end(),
+                       [&](const Chunk& x, const Chunk& y) { return weight(x) > weight(y); });
+      chunk_n = std::max(chunk_n, (size_t)3 * ps.chunks.size());
+    }
+    HIP_TRY(ctx->g_chunks.ensure(chunk_n * sizeof(int32_t)));
+    return SRHIP_OK;
+  }
+
+  int launch(int pi, const GradPass& ps, hipEvent_t ev0) {
+    const int nch = (int)ps.chunks.size();
+    // the device list, (slot, c0, set) per chunk, through pinned staging; stream order: the copy follows
+    // the previous pass's kernel, which has read its chunk list
+    const size_t list_bytes = (size_t)3 * nch * sizeof(int32_t);
+    HIP_TRY(ctx->h_gchunks[pi].ensure(list_bytes));
+    int32_t* const list = (int32_t*)ctx->h_gchunks[pi].p;
+    for (int c = 0; c < nch; ++c) {
+      list[3 * c] = ps.chunks[c].slot;
+      list[3 * c + 1] = ps.chunks[c].c0;
+      list[3 * c + 2] = ps.chunks[c].tree;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->g_chunks.p, list, list_bytes, hipMemcpyHostToDevice, ctx->stream));
+    GradRowsetArgs a{};
+    a.code = (const Ins*)P->d_gcode.p;
+    a.prog_off = (const int32_t*)P->d_goff.p;
+    a.chunks = (const int32_t*)ctx->g_chunks.p;
+    a.packed = rb.packed;
+    a.set_off = rb.d_set_off;
+    a.set_m = rb.d_set_m;
+    a.out = (double*)ctx->h_gred[pi].p;
+    a.ld = 0;
+    a.nchunks = nch;
+    a.nfeat = (int32_t)ds->nfeat;
+    a.gd_nd = 0;
+    a.loss_kind = loss->kind;
+    a.loss_p0 = loss->p0;
+    a.weighted = ds->weighted ? 1 : 0;
+    a.max_steps = P->gmax_len;
+    if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));
+    HIP_TRY(launch_grad_rowsets(P->dtype, ps.kt, a, max_ld[pi], ctx->stream));
+    return SRHIP_OK;
+  }
+
+  double wsum(const GradItem& it) const { return ds->weighted ? rb.wsum[it.tree] : (double)rb.m[it.tree]; }
+  const double* decide_inputs(const GradItem& it) {
+    fill_decide_inputs(sums.data(), P->ntrees, ds->nfeat, rb.fstat.data() + (size_t)it.tree * ds->nfeat, rb.m[it.tree]);
+    return sums.data();
+  }
+
+  // (rare) the exact per-operator-node pass on a view made from each item's own set
+  int settle(const std::vector<GradItem>& items, const std::vector<int32_t>& und, uint8_t* ok) {
+    for (size_t u = 0; u < und.size(); ++u) {
+      const GradItem& it = items[und[u]];
+      View v{};
+      int rc = make_view(ctx, ds, rb.rows + rb.row_off[it.tree], rb.m[it.tree], true, v);
+      if (rc) return rc;
+      rc = precise_decide(ctx, ds, P, v, &it.slot, 1, true, ok + u);
+      if (rc) return rc;
+    }
+    return SRHIP_OK;
+  }
+};
+
+// The evaluation primitive: every item's loss (+Inf where did_succeed fails), gradient and ok, in two
+// passes on the stream (gradient chunks, then value-only chunks) and one synchronisation.
+// timed: HIP events around the gradient kernels (srhip_last_kernel_ms).  The optimiser's launches go
+// without: two timing events per launch cost C4 ~5 % (149-153 against 141-145 ms on one box).
+template <class Backend>
+static int eval_grad_items_on(srhip_ctx* ctx, srhip_program* P, Backend& be, const std::vector<GradItem>& items,
+                              bool timed) {
+  // tangent width of the gradient pass: a chunk carries the primal plus kt tangents, so trees with
+  // few constants waste most of an 8-wide chunk; estimated cost per chunk ~ (3 + kt) (the primal's
+  // transcendentals and derivative factors cost about three tangent updates).  Values and the
+  // tangents of each constant do not depend on kt (independent components, same primal code; kt = 0
+  // is the value-only pass).
+  int64_t cost4 = 0, cost8 = 0;
+  for (const GradItem& it : items) {
+    if (P->ginfo[it.slot].static_fail || it.value_only) continue;
+    const int nc = std::max(P->info[it.tree].nconst, 1);
+    cost4 += (int64_t)((nc + 3) / 4) * (3 + 4);
+    cost8 += (int64_t)((nc + GRAD_KT - 1) / GRAD_KT) * (3 + GRAD_KT);
+  }
+  const char* kte = env_get("SRHIP_GRAD_KT");  // tuning / tests: force 4 or 8
+  int kt = cost4 < cost8 ? 4 : GRAD_KT;
+  if (kte && (atoi(kte) == 4 || atoi(kte) == GRAD_KT)) kt = atoi(kte);
+  GradPass pass[2];
+  pass[0].kt = kt;
+  pass[1].kt = 0;
+  for (size_t i = 0; i < items.size(); ++i) {
+    const GradItem& it = items[i];
+    *it.f = INFINITY;
+    if (it.ok) *it.ok = 0;
+    const int nc = P->info[it.tree].nconst;
+    if (!it.value_only)
+      for (int k = 0; k < nc; ++k) it.g[k] = 0.0;
+    if (P->ginfo[it.slot].static_fail) continue;
+    GradPass& ps = pass[it.value_only ? 1 : 0];
+    const int span = it.value_only ? 1 : std::max(nc, 1);
+    for (int c0 = 0; c0 < span; c0 += std::max(ps.kt, 1)) ps.chunks.push_back(Chunk{it.slot, c0, (int32_t)i, it.tree});
+  }
+  if (pass[0].chunks.empty() && pass[1].chunks.empty()) {  // a patched gradient program may still be uploading from P->gcode
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SRHIP_OK;
+  }
+  int rc = be.prepare(pass);
+  if (rc) return rc;
+  bool first = true;
+  for (int pi = 0; pi < 2; ++pi) {
+    GradPass& ps = pass[pi];
+    if (ps.chunks.empty()) continue;
+    HIP_TRY(ctx->h_gred[pi].ensure(ps.chunks.size() * (ps.kt + 2) * sizeof(double), hipHostMallocCoherent));
+    rc = be.launch(pi, ps, first && timed ? ctx->ev0 : nullptr);
+    if (rc) return rc;
+    first = false;
+    ps.red = (const double*)ctx->h_gred[pi].p;
+  }
+  if (timed) HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->timed = timed;
+  ctx->last_ev0 = ctx->ev0;
+  ctx->last_ev1 = ctx->ev1;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  std::vector<int32_t> undecided;  // items
+  for (const GradPass& ps : pass) {
+    const int nch = (int)ps.chunks.size();
+    for (int c = 0; c < nch; ++c) {
+      const Chunk& ch = ps.chunks[c];
+      const GradItem& it = items[ch.item];
+      const double* r = ps.red + (size_t)c * (ps.kt + 2);
+      const int nc = P->info[it.tree].nconst;
+      const double wsum = be.wsum(it);
+      for (int j = 0; j < ps.kt && ch.c0 + j < nc; ++j) it.g[ch.c0 + j] = r[1 + j] / wsum;
+      if (ch.c0 == 0) {
+        const int st = decide_tree(P->ginfo[it.slot], *P, be.ds->nfeat, be.decide_inputs(it), r[ps.kt + 1]);
+        *it.f = st == 1 ? INFINITY : r[0] / wsum;
+        if (it.ok) *it.ok = st != 1;
+        if (st == 2) undecided.push_back(ch.item);
+      }
+    }
+  }
+  if (g_stats_on)
+    for (const GradItem& it : items) {
+      int64_t* c = g_items[it.value_only ? 1 : 0][items.size() > 64 ? 1 : 0];
+      c[0] += 1;
+      c[1] += !std::isfinite(*it.f);
+    }
+  if (!undecided.empty()) {
+    std::vector<uint8_t> uok(undecided.size());
+    rc = be.settle(items, undecided, uok.data());
+    if (rc) return rc;
+    for (size_t u = 0; u < undecided.size(); ++u)
+      if (!uok[u]) {
+        const GradItem& it = items[undecided[u]];
+        *it.f = INFINITY;
+        if (it.ok) *it.ok = 0;
+      }
+  }
+  return SRHIP_OK;
+}
+// on the view's rows, or (rb given: it replaces the view) every item on its tree's own row set
 static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
-                           const View& v, const std::vector<GradItem>& items, bool timed = true,
-                           const RowsetBatch* rb = nullptr);
+                           const View& v, const std::vector<GradItem>& items, bool timed, const RowsetBatch* rb) {
+  if (rb) {
+    RowsetBackend be{ctx, ds, P, loss, *rb};
+    return eval_grad_items_on(ctx, P, be, items, timed);
+  }
+  ViewBackend be{ctx, ds, P, loss, v};
+  return eval_grad_items_on(ctx, P, be, items, timed);
+}
+
 // Loss and gradient for `trees` at the program's current constants: f[t], g[coff[t] ..], ok[t]
 // (nullable; did_succeed -- a tree can succeed with an overflowing loss: f = Inf, ok = 1), plus the
 // items in `extra` (speculative slots, already instantiated; their instructions [spec_lo, spec_hi)
@@ -220,377 +534,6 @@ static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, 
   // on an error return, drain the stream before the caller can destroy or recompile the program
   if (rc) (void)hipStreamSynchronize(ctx->stream);
   return rc;
-}
-// The evaluation primitive's second backend: every item on its tree's own row set (srhip_grad_rowsets.hip).
-// One single-wave workgroup per chunk (slot, c0, set), launched in descending set length x tree cost; the
-// waves write the final (kt + 2) records straight into the pinned staging, so a pass is one launch.  Each
-// item is decided on its own set's statistics (feature sums, non-finite counts, rows, weight sum); an
-// undecided item (a near-overflow sum) is settled by the precise pass over a view gathered from its set.
-static int eval_grad_items_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
-                                   const RowsetBatch& rb, const std::vector<GradItem>& items, bool timed) {
-  const int dtype = P->dtype;
-  const bool weighted = ds->weighted;
-  // the tangent width, as eval_grad_items picks it (no result depends on it)
-  int64_t cost4 = 0, cost8 = 0;
-  for (const GradItem& it : items) {
-    if (P->ginfo[it.slot].static_fail || it.value_only) continue;
-    const int nc = std::max(P->info[it.tree].nconst, 1);
-    cost4 += (int64_t)((nc + 3) / 4) * (3 + 4);
-    cost8 += (int64_t)((nc + GRAD_KT - 1) / GRAD_KT) * (3 + GRAD_KT);
-  }
-  const char* kte = env_get("SRHIP_GRAD_KT");
-  int kt = cost4 < cost8 ? 4 : GRAD_KT;
-  if (kte && (atoi(kte) == 4 || atoi(kte) == GRAD_KT)) kt = atoi(kte);
-  struct Pass {
-    int kt;
-    std::vector<int32_t> chunks, chunk_item;  // [nch][3] (slot, c0, set), and each chunk's item
-    const double* red = nullptr;
-    int max_ld = 0;
-  } pass[2];
-  pass[0].kt = kt;
-  pass[1].kt = 0;
-  for (size_t i = 0; i < items.size(); ++i) {
-    const GradItem& it = items[i];
-    *it.f = INFINITY;
-    if (it.ok) *it.ok = 0;
-    const int nc = P->info[it.tree].nconst;
-    if (!it.value_only)
-      for (int k = 0; k < nc; ++k) it.g[k] = 0.0;
-    if (P->ginfo[it.slot].static_fail) continue;
-    if (!rb.staged[it.tree]) return fail(SRHIP_ERR_INVALID, "tree %d: its row set is not staged", (int)it.tree);
-    Pass& ps = pass[it.value_only ? 1 : 0];
-    const int span = it.value_only ? 1 : std::max(nc, 1);
-    for (int c0 = 0; c0 < span; c0 += std::max(ps.kt, 1)) {
-      ps.chunks.push_back(it.slot);
-      ps.chunks.push_back(c0);
-      ps.chunks.push_back(it.tree);
-      ps.chunk_item.push_back((int32_t)i);
-    }
-  }
-  if (pass[0].chunk_item.empty() && pass[1].chunk_item.empty()) {  // a patched gradient program may still be uploading
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SRHIP_OK;
-  }
-  size_t chunk_n = 0;
-  for (Pass& ps : pass) {
-    const int nch = (int)ps.chunk_item.size();
-    if (nch == 0) continue;
-    std::vector<int32_t> by(nch);
-    std::iota(by.begin(), by.end(), 0);
-    auto weight = [&](int32_t c) { return (double)rb.m[ps.chunks[3 * c + 2]] * P->ginfo[ps.chunks[3 * c]].cost; };
-    std::stable_sort(by.begin(), by.end(), [&](int32_t x, int32_t y) { return weight(x) > weight(y); });
-    std::vector<int32_t> chunks2(ps.chunks.size()), item2(nch);
-    for (int pos = 0; pos < nch; ++pos) {
-      const int32_t k = by[pos];
-      for (int j = 0; j < 3; ++j) chunks2[3 * pos + j] = ps.chunks[3 * k + j];
-      item2[pos] = ps.chunk_item[k];
-      const int ld = (rb.m[ps.chunks[3 * k + 2]] + GRAD_ROWSET_RB - 1) / GRAD_ROWSET_RB * GRAD_ROWSET_RB;
-      ps.max_ld = std::max(ps.max_ld, ld);
-    }
-    ps.chunks.swap(chunks2);
-    ps.chunk_item.swap(item2);
-    chunk_n = std::max(chunk_n, ps.chunks.size());
-  }
-  HIP_TRY(ctx->g_chunks.ensure(chunk_n * sizeof(int32_t)));
-  bool first = true;
-  for (int pi = 0; pi < 2; ++pi) {
-    Pass& ps = pass[pi];
-    const int nch = (int)ps.chunk_item.size();
-    if (nch == 0) continue;
-    HIP_TRY(ctx->h_gred[pi].ensure((size_t)nch * (ps.kt + 2) * sizeof(double), hipHostMallocCoherent));
-    HIP_TRY(ctx->h_gchunks[pi].ensure(ps.chunks.size() * sizeof(int32_t)));
-    memcpy(ctx->h_gchunks[pi].p, ps.chunks.data(), ps.chunks.size() * sizeof(int32_t));
-    // stream order: this copy follows the previous pass's kernel, which has read its chunk list
-    HIP_TRY(hipMemcpyAsync(ctx->g_chunks.p, ctx->h_gchunks[pi].p, ps.chunks.size() * sizeof(int32_t),
-                           hipMemcpyHostToDevice, ctx->stream));
-    GradRowsetArgs a{};
-    a.code = (const Ins*)P->d_gcode.p;
-    a.prog_off = (const int32_t*)P->d_goff.p;
-    a.chunks = (const int32_t*)ctx->g_chunks.p;
-    a.packed = rb.packed;
-    a.set_off = rb.d_set_off;
-    a.set_m = rb.d_set_m;
-    a.out = (double*)ctx->h_gred[pi].p;
-    a.ld = 0;
-    a.nchunks = nch;
-    a.nfeat = (int32_t)ds->nfeat;
-    a.gd_nd = 0;
-    a.loss_kind = loss->kind;
-    a.loss_p0 = loss->p0;
-    a.weighted = weighted ? 1 : 0;
-    a.max_steps = P->gmax_len;
-    if (first && timed) HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    first = false;
-    HIP_TRY(launch_grad_rowsets(dtype, ps.kt, a, ps.max_ld, ctx->stream));
-    ps.red = (const double*)ctx->h_gred[pi].p;
-  }
-  if (timed) HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->timed = timed;
-  ctx->last_ev0 = ctx->ev0;
-  ctx->last_ev1 = ctx->ev1;
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  // decisions: each item on its own set's statistics, in the partials layout decide_tree reads
-  const int64_t nf = ds->nfeat;
-  std::vector<double> sums(2 * (size_t)P->ntrees + 2 * nf + 1, 0.0);
-  double* const tail = sums.data() + 2 * (size_t)P->ntrees;
-  std::vector<int32_t> undecided_item;
-  for (const Pass& ps : pass) {
-    const int nch = (int)ps.chunk_item.size();
-    for (int c = 0; c < nch; ++c) {
-      const GradItem& it = items[ps.chunk_item[c]];
-      const int32_t c0 = ps.chunks[3 * c + 1];
-      const double* r = ps.red + (size_t)c * (ps.kt + 2);
-      const int nc = P->info[it.tree].nconst;
-      const double wsum = weighted ? rb.wsum[it.tree] : (double)rb.m[it.tree];
-      for (int j = 0; j < ps.kt && c0 + j < nc; ++j) it.g[c0 + j] = r[1 + j] / wsum;
-      if (c0 == 0) {
-        const FeatStat* fs = rb.fstat.data() + (size_t)it.tree * nf;
-        for (int64_t fi = 0; fi < nf; ++fi) {
-          tail[2 * fi] = fs[fi].sum;
-          tail[2 * fi + 1] = (double)fs[fi].nonfinite;
-        }
-        tail[2 * nf] = (double)rb.m[it.tree];
-        const int st = decide_tree(P->ginfo[it.slot], *P, nf, sums.data(), r[ps.kt + 1]);
-        *it.f = st == 1 ? INFINITY : r[0] / wsum;
-        if (it.ok) *it.ok = st != 1;
-        if (st == 2) undecided_item.push_back(ps.chunk_item[c]);
-      }
-    }
-  }
-  if (g_stats_on)
-    for (const GradItem& it : items) {
-      int64_t* c = g_items[it.value_only ? 1 : 0][items.size() > 64 ? 1 : 0];
-      c[0] += 1;
-      c[1] += !std::isfinite(*it.f);
-    }
-  // near-overflow sums (rare): the exact per-operator-node pass on a view made from the item's own set
-  for (int32_t ui : undecided_item) {
-    const GradItem& it = items[ui];
-    View v{};
-    int rc = make_view(ctx, ds, rb.rows + rb.row_off[it.tree], rb.m[it.tree], true, v);
-    if (rc) return rc;
-    uint8_t uok = 0;
-    const int32_t slot = it.slot;
-    rc = precise_decide(ctx, ds, P, v, &slot, 1, true, &uok);
-    if (rc) return rc;
-    if (!uok) {
-      *it.f = INFINITY;
-      if (it.ok) *it.ok = 0;
-    }
-  }
-  return SRHIP_OK;
-}
-
-// timed: HIP events around the gradient kernels (srhip_last_kernel_ms).  The optimiser's launches go
-// without: two timing events per launch cost C4 ~5 % (149-153 against 141-145 ms on one box).
-static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
-                           const View& v, const std::vector<GradItem>& items, bool timed, const RowsetBatch* rb) {
-  if (rb) return eval_grad_items_rowsets(ctx, ds, P, loss, *rb, items, timed);
-  const int dtype = P->dtype;
-  const bool weighted = ds->weighted;
-  const double wsum = weighted ? v.sum_w : (double)v.m;
-  // tangent width of the gradient pass: a chunk carries the primal plus kt tangents, so trees with
-  // few constants waste most of an 8-wide chunk; estimated cost per chunk ~ (3 + kt) (the primal's
-  // transcendentals and derivative factors cost about three tangent updates).  Values and the
-  // tangents of each constant do not depend on kt (independent components, same primal code; kt = 0
-  // is the value-only pass).
-  int64_t cost4 = 0, cost8 = 0;
-  for (const GradItem& it : items) {
-    if (P->ginfo[it.slot].static_fail || it.value_only) continue;
-    const int nc = std::max(P->info[it.tree].nconst, 1);
-    cost4 += (int64_t)((nc + 3) / 4) * (3 + 4);
-    cost8 += (int64_t)((nc + GRAD_KT - 1) / GRAD_KT) * (3 + GRAD_KT);
-  }
-  const char* kte = env_get("SRHIP_GRAD_KT");  // tuning / tests: force 4 or 8
-  int kt = cost4 < cost8 ? 4 : GRAD_KT;
-  if (kte && (atoi(kte) == 4 || atoi(kte) == GRAD_KT)) kt = atoi(kte);
-  // two passes on the stream (gradient chunks, then value-only chunks), one synchronisation
-  struct Pass {
-    int kt;
-    std::vector<int32_t> chunks, chunk_item;
-    const double* red = nullptr;  // the reduced records, in the context's pinned staging
-    LaunchPlan L;
-  } pass[2];
-  pass[0].kt = kt;
-  pass[1].kt = 0;
-  for (size_t i = 0; i < items.size(); ++i) {
-    const GradItem& it = items[i];
-    *it.f = INFINITY;
-    if (it.ok) *it.ok = 0;
-    const int nc = P->info[it.tree].nconst;
-    if (!it.value_only)
-      for (int k = 0; k < nc; ++k) it.g[k] = 0.0;
-    if (P->ginfo[it.slot].static_fail) continue;
-    Pass& ps = pass[it.value_only ? 1 : 0];
-    const int span = it.value_only ? 1 : std::max(nc, 1);
-    for (int c0 = 0; c0 < span; c0 += std::max(ps.kt, 1)) {
-      ps.chunks.push_back(it.slot);
-      ps.chunks.push_back(c0);
-      ps.chunk_item.push_back((int32_t)i);
-    }
-  }
-  const int nch0 = (int)pass[0].chunks.size() / 2, nch1 = (int)pass[1].chunks.size() / 2;
-  if (nch0 + nch1 == 0) {  // a patched gradient program may still be uploading from P->gcode
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SRHIP_OK;
-  }
-  // buffers sized for both passes before the first launch (no reallocation under a queued kernel)
-  size_t slab_n = 0, red_n = 0, chunk_n = 0;
-  for (Pass& ps : pass) {
-    const int nch = (int)ps.chunks.size() / 2;
-    if (nch == 0) continue;
-    ps.L = grad_plan(ctx, v.m, nch);
-    // launch order: descending estimated cost, dealt round-robin over the tree groups (each group's
-    // range stays contiguous), so every group gets the same cost mix and its waves -- which claim
-    // chunks dynamically -- start with the longest ones.  Records are read back by position.
-    if (nch > 1) {
-      std::vector<int32_t> by(nch);
-      std::iota(by.begin(), by.end(), 0);
-      std::stable_sort(by.begin(), by.end(), [&](int32_t x, int32_t y) {
-        return P->ginfo[ps.chunks[2 * x]].cost > P->ginfo[ps.chunks[2 * y]].cost;
-      });
-      const int G = ps.L.groups, tpg = ps.L.tpg;
-      std::vector<int32_t> fill(G, 0), chunks2(ps.chunks.size()), item2(nch);
-      int g = 0;
-      for (int32_t k : by) {
-        while (fill[g] >= std::min(tpg, nch - g * tpg)) g = (g + 1) % G;
-        const int pos = g * tpg + fill[g]++;
-        chunks2[2 * pos] = ps.chunks[2 * k];
-        chunks2[2 * pos + 1] = ps.chunks[2 * k + 1];
-        item2[pos] = ps.chunk_item[k];
-        g = (g + 1) % G;
-      }
-      ps.chunks.swap(chunks2);
-      ps.chunk_item.swap(item2);
-    }
-    slab_n = std::max(slab_n, (size_t)nch * ps.L.nrb * (ps.kt + 2));
-    red_n = std::max(red_n, (size_t)nch * (ps.kt + 2));
-    chunk_n = std::max(chunk_n, ps.chunks.size());
-  }
-  HIP_TRY(ctx->g_chunks.ensure(chunk_n * sizeof(int32_t)));
-  HIP_TRY(ctx->g_slab.ensure(slab_n * sizeof(double)));
-  HIP_TRY(ctx->g_red.ensure(red_n * sizeof(double)));
-  const int K = P->gkmax <= 2 ? 2 : (P->gkmax <= 4 ? 4 : 8);  // stack slots of the kernel variant
-  bool first = true;
-  for (int pi = 0; pi < 2; ++pi) {
-    Pass& ps = pass[pi];
-    const int nch = (int)ps.chunks.size() / 2;
-    if (nch == 0) continue;
-    // pinned staging both ways (a pageable source or destination makes the runtime stage the copy
-    // through its own buffer, synchronously); stream order: this copy follows the previous pass's
-    // kernel, which has read its chunk list
-    HIP_TRY(ctx->h_gred[pi].ensure((size_t)nch * (ps.kt + 2) * sizeof(double), hipHostMallocCoherent));
-    GradArgs a{};
-    // SRHIP_GRAD_INLINE_MAX (0: always copy the list), read per pass through the environment cache
-    // so a test can compare both forms in one process
-    const char* ie = env_get("SRHIP_GRAD_INLINE_MAX");
-    const int inline_max = ie && *ie ? std::max(0, std::min(atoi(ie), GRAD_INLINE)) : GRAD_INLINE;
-    const bool inl = nch <= inline_max;
-    if (inl) {  // in the kernel arguments
-      memcpy(a.inl, ps.chunks.data(), ps.chunks.size() * sizeof(int32_t));
-    } else {
-      HIP_TRY(ctx->h_gchunks[pi].ensure(ps.chunks.size() * sizeof(int32_t)));
-      memcpy(ctx->h_gchunks[pi].p, ps.chunks.data(), ps.chunks.size() * sizeof(int32_t));
-      HIP_TRY(hipMemcpyAsync(ctx->g_chunks.p, ctx->h_gchunks[pi].p, ps.chunks.size() * sizeof(int32_t),
-                             hipMemcpyHostToDevice, ctx->stream));
-    }
-    a.code = (const Ins*)P->d_gcode.p;
-    a.prog_off = (const int32_t*)P->d_goff.p;
-    a.chunks = inl ? nullptr : (const int32_t*)ctx->g_chunks.p;
-    a.X = v.X;
-    a.y = v.y;
-    a.w = weighted ? v.w : nullptr;
-    a.slab = (double*)ctx->g_slab.p;
-    a.ld = v.ld;
-    a.nvalid = v.m;
-    a.nchunks = nch;
-    a.nfeat = v.nfeat_x >= 0 ? v.nfeat_x : (int32_t)ds->nfeat;
-    a.gd_nd = v.nd_x;
-    a.rb_rows = ps.L.rb_rows;
-    a.nrb = ps.L.nrb;
-    a.chunks_per_group = ps.L.tpg;
-    a.loss_kind = loss->kind;
-    a.loss_p0 = loss->p0;
-    a.weighted = weighted ? 1 : 0;
-    a.max_steps = P->gmax_len;
-    if (first && timed) HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));  // srhip_last_kernel_ms: the gradient kernels
-    first = false;
-    // value-only screening (SRHIP_GRAD_SCREEN = the fewest value-only chunks screened; default 0 =
-    // off): row block 0 of every chunk first, in a launch of its own, then the other blocks, where a
-    // chunk whose block-0 check statistic is already non-finite is skipped.  Records of evaluated
-    // blocks are the same computation as in one launch, so losses and decisions are bit-identical
-    // (test_value_only_screening_is_exact).  C4 (~40 % of its trial points overflow), same box:
-    // off 173.6-177.9 ms, every pass 190-193, passes of >= 16 chunks 176.8-179.6 -- the extra launch
-    // costs what the skipped blocks save at 100k rows.
-    const int screen_min = env_int_opt("SRHIP_GRAD_SCREEN", 0);
-    if (ps.kt == 0 && screen_min > 0 && nch >= screen_min && ps.L.nrb > 1) {
-      GradArgs sa = a;
-      const int tpg_s = 2 * GRAD_WAVES;
-      sa.chunks_per_group = tpg_s;
-      HIP_TRY(launch_grad(dtype, K, 0, sa, dim3(1, (nch + tpg_s - 1) / tpg_s), ctx->stream));
-      a.block0 = 1;
-      a.screened = 1;
-      HIP_TRY(launch_grad(dtype, K, 0, a, dim3(ps.L.nrb - 1, ps.L.groups), ctx->stream));
-    } else {
-      HIP_TRY(launch_grad(dtype, K, ps.kt, a, dim3(ps.L.nrb, ps.L.groups), ctx->stream));
-    }
-    // the reduction writes the records straight into coherent pinned host memory (no copy on the stream)
-    HIP_TRY(launch_grad_reduce(dtype, ps.kt, (const double*)ctx->g_slab.p, ps.L.nrb, nch, (double*)ctx->h_gred[pi].p,
-                               ctx->stream));
-    ps.red = (const double*)ctx->h_gred[pi].p;
-  }
-  if (timed) HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->timed = timed;
-  ctx->last_ev0 = ctx->ev0;
-  ctx->last_ev1 = ctx->ev1;
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  // decision inputs in the partials layout: only the feature statistics and the row count are read
-  std::vector<double> sums(2 * (size_t)P->ntrees + 2 * ds->nfeat + 1, 0.0);
-  for (int64_t fi = 0; fi < ds->nfeat; ++fi) {
-    sums[2 * (size_t)P->ntrees + 2 * fi] = v.stats[fi].sum;
-    sums[2 * (size_t)P->ntrees + 2 * fi + 1] = (double)v.stats[fi].nonfinite;
-  }
-  sums.back() = (double)v.m;
-  std::vector<int32_t> undecided, undecided_item;
-  for (const Pass& ps : pass) {
-    const int nch = (int)ps.chunks.size() / 2;
-    for (int c = 0; c < nch; ++c) {
-      const GradItem& it = items[ps.chunk_item[c]];
-      const int32_t c0 = ps.chunks[2 * c + 1];
-      const double* r = ps.red + (size_t)c * (ps.kt + 2);
-      const int nc = P->info[it.tree].nconst;
-      for (int j = 0; j < ps.kt && c0 + j < nc; ++j) it.g[c0 + j] = r[1 + j] / wsum;
-      if (c0 == 0) {
-        const int st = decide_tree(P->ginfo[it.slot], *P, ds->nfeat, sums.data(), r[ps.kt + 1]);
-        *it.f = st == 1 ? INFINITY : r[0] / wsum;
-        if (it.ok) *it.ok = st != 1;
-        if (st == 2) {
-          undecided.push_back(it.slot);
-          undecided_item.push_back(ps.chunk_item[c]);
-        }
-      }
-    }
-  }
-  if (g_stats_on)
-    for (const GradItem& it : items) {
-      int64_t* c = g_items[it.value_only ? 1 : 0][items.size() > 64 ? 1 : 0];
-      c[0] += 1;
-      c[1] += !std::isfinite(*it.f);
-    }
-  // near-overflow sums: the exact per-operator-node pass on the gradient program decides, so the
-  // objective is eval_loss's (L(Inf) exactly where did_succeed fails)
-  if (!undecided.empty()) {
-    std::vector<uint8_t> uok(undecided.size());
-    const int rc = precise_decide(ctx, ds, P, v, undecided.data(), (int32_t)undecided.size(), true, uok.data());
-    if (rc) return rc;
-    for (size_t u = 0; u < undecided.size(); ++u)
-      if (!uok[u]) {
-        const GradItem& it = items[undecided_item[u]];
-        *it.f = INFINITY;
-        if (it.ok) *it.ok = 0;
-      }
-  }
-  return SRHIP_OK;
 }
 
 namespace {
@@ -897,8 +840,8 @@ static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program
   const int spec_cap = spe && *spe ? std::max(0, std::min(atoi(spe), 4096)) : 32;
   // speculate only in the pipeline's tail (SRHIP_OPTIM_SPEC_ACTIVE, default 64 active trees), at most
   // SRHIP_OPTIM_SPEC_DEPTH (default 64) points per tree and launch
-  const size_t SPEC_MAX_ACTIVE = (size_t)std::max(0, env_int_opt("SRHIP_OPTIM_SPEC_ACTIVE", 64));
-  const int SPEC_MAX_DEPTH = std::max(1, env_int_opt("SRHIP_OPTIM_SPEC_DEPTH", 64));
+  const size_t SPEC_MAX_ACTIVE = (size_t)std::max(0, env_int("SRHIP_OPTIM_SPEC_ACTIVE", 64));
+  const int SPEC_MAX_DEPTH = std::max(1, env_int("SRHIP_OPTIM_SPEC_DEPTH", 64));
   if (P->gspec_cap != spec_cap) {
     P->gspec_cap = spec_cap;  // the next gradient compile allocates the slots (a full compile)
     P->grad_ready = false;
@@ -934,7 +877,7 @@ static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program
     const double t0 = now_s();
     for (int32_t t : act) {  // only the active trees' constants change (get_constants order per tree)
       const double* c = xe.data() + coff[t];
-      set_consts_rec(P->nodes.data() + P->offsets[t], 0, c);
+      set_consts(P->nodes.data() + P->offsets[t], 0, c);
     }
     // the patch scans just the trees whose constants moved (a union if an earlier hint is pending;
     // no hint at all -- an unknown change -- keeps the full scan)
@@ -1223,8 +1166,6 @@ int optimize_split(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, co
   if (G == 1) return bfgs_pipelined(ctx, ds, P, loss, v, trees, coff, iterations, g_tol, starts, best_x, best_f, fcalls);
   std::vector<std::vector<int32_t>> grp(G);
   for (size_t i = 0; i < trees.size(); ++i) grp[i % G].push_back(trees[i]);
-  const srhip_operators ops{(int32_t)P->binops.size(), (int32_t)P->unaops.size(), P->binops.data(),
-                            P->unaops.data()};
   struct Part {
     srhip_program* P = nullptr;
     std::vector<int64_t> coff;
@@ -1243,14 +1184,8 @@ int optimize_split(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, co
   for (int gi = 1; gi < G; ++gi) {
     Part& q = part[gi];
     const std::vector<int32_t>& tb = grp[gi];
-    std::vector<srhip_node> nodes2;
-    std::vector<int64_t> offs2(1, 0);
-    for (int32_t t : tb) {
-      nodes2.insert(nodes2.end(), P->nodes.begin() + P->offsets[t], P->nodes.begin() + P->offsets[t + 1]);
-      offs2.push_back((int64_t)nodes2.size());
-    }
     const int32_t n2 = (int32_t)tb.size();
-    const int rc = srhip_program_create(aux[gi - 1], P->dtype, nodes2.data(), offs2.data(), n2, &ops, &q.P);
+    const int rc = subprogram(aux[gi - 1], P, tb, &q.P);
     if (rc) return rc;
     // the caller's derived view serves every group: the same column numbering
     q.P->gdspec = P->gdspec;
@@ -1299,6 +1234,84 @@ int optimize_split(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, co
   return SRHIP_OK;
 }
 
+// ---- the steps the optimiser's entry points share (each entry point keeps its own baseline, generator
+// order, run and re-score) -------------------------------------------------------------------------
+int check_optim_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
+                     const srhip_optim_options* opt) {
+  if (opt->iterations < 0 || opt->nrestarts < 0) return fail(SRHIP_ERR_INVALID, "negative iterations / restarts");
+  const int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant optimisation needs Float32 / Float64");
+  return SRHIP_OK;
+}
+// One perturbed start of the constant x0k (src/ConstantOptimization.jl:53-60: c * (1 + randn/2)).
+// Float32 trees perturb in T as the reference does (node.val * (T(1) + T(1//2) * randn(T))): a Float32
+// normal draw and Float32 arithmetic, the start rounded like the constant it replaces.  A caller-supplied
+// start (given) replaces the draw -- the generator is not advanced; a Float32 program rounds it to Float32.
+double perturbed_start(double x0k, std::mt19937_64& rng, std::normal_distribution<double>& randn, bool f32,
+                       const double* given) {
+  double xs;
+  if (given) {
+    xs = *given;
+  } else if (f32) {
+    const float r = (float)randn(rng);
+    xs = (double)((float)x0k * (1.0f + 0.5f * r));
+  } else {
+    xs = x0k * (1.0 + 0.5 * randn(rng));
+  }
+  return f32 ? (double)(float)xs : xs;
+}
+// starts[1 ..] (the restarts; starts[0] is x0) to the caller's [nrestarts][sum nconst], if wanted
+void copy_starts_out(const std::vector<std::vector<double>>& starts, double* starts_out) {
+  if (!starts_out) return;
+  for (size_t s = 1; s < starts.size(); ++s)
+    std::copy(starts[s].begin(), starts[s].end(), starts_out + (s - 1) * starts[s].size());
+}
+// the thread's timing counters and statistics (SRHIP_OPTIM_TIMING), before an optimiser run
+void reset_optim_counters(bool stats_on, bool launch_log) {
+  g_t_compile = g_t_eval = g_t_host = 0.0;
+  g_patch_scan_s = g_patch_copy_s = 0.0;
+  g_n_launch = 0;
+  g_stats_on = stats_on;
+  g_launch_log = launch_log;
+  for (int64_t& h : g_hist) h = 0;
+  g_nonfinite_trials = 0;
+  g_spec_launched = g_spec_used = 0;
+  for (auto& a : g_items)
+    for (auto& b : a) b[0] = b[1] = 0;
+}
+// after a failed run: the program back at the constants it came with
+void restore_constants(srhip_program& P, const std::vector<double>& x0) {
+  set_all_consts(P, x0.data());
+  compile_program(P);
+  upload_program(P);
+}
+// accept where the best minimum beats the baseline (src/ConstantOptimization.jl:70-78): out_improved[t],
+// and the constants to return -- best_x of the accepted trees, x0 of the others
+std::vector<double> accept_against_baseline(const std::vector<double>& x0, const std::vector<int64_t>& coff,
+                                            const std::vector<double>& best_x, const std::vector<double>& best_f,
+                                            const std::vector<double>& base, uint8_t* out_improved) {
+  std::vector<double> final_x = x0;
+  for (size_t t = 0; t < base.size(); ++t) {
+    const bool better = best_f[t] < base[t];
+    out_improved[t] = better ? 1 : 0;
+    if (better)
+      for (int64_t k = coff[t]; k < coff[t + 1]; ++k) final_x[k] = best_x[k];
+  }
+  return final_x;
+}
+int install_constants(srhip_program& P, const std::vector<double>& final_x) {
+  set_all_consts(P, final_x.data());
+  const int rc = compile_program(P);
+  return rc ? rc : upload_program(P);
+}
+// num_evals bookkeeping (src/ConstantOptimization.jl:51,65,79): the objective calls of every start
+// (result.f_calls), plus one for the re-score of an accepted tree; 0 for a tree left alone
+void report_fcalls(const std::vector<int64_t>& fcalls, const uint8_t* out_improved, int64_t* out_fcalls) {
+  if (!out_fcalls) return;
+  for (size_t t = 0; t < fcalls.size(); ++t) out_fcalls[t] = fcalls[t] + out_improved[t];
+}
+
 }  // namespace
 
 extern "C" {
@@ -1308,10 +1321,8 @@ int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srh
                                     const srhip_optim_options* opt, const double* starts_in, double* starts_out,
                                     double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
   if (!opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
-  if (opt->iterations < 0 || opt->nrestarts < 0) return fail(SRHIP_ERR_INVALID, "negative iterations / restarts");
-  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  int rc = check_optim_args(ctx, ds, P, loss, opt);
   if (rc) return rc;
-  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant optimisation needs Float32 / Float64");
   HIP_TRY(hipSetDevice(ctx->device));
   const int32_t nt = P->ntrees;
   // baseline = f(tree) with the evaluator itself (src/ConstantOptimization.jl:49)
@@ -1330,53 +1341,29 @@ int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srh
   if (rc) return rc;
   const std::vector<int64_t> coff = const_offsets(*P);
   const std::vector<double> x0 = get_all_consts(*P);
+  const int64_t nall = (int64_t)x0.size();
   std::vector<int32_t> trees;  // trees with constants (nconst == 0: nothing to optimise, :35)
   for (int32_t t = 0; t < nt; ++t)
     if (P->info[t].nconst > 0 && !P->info[t].static_fail) trees.push_back(t);
   std::vector<double> best_x = x0, best_f(nt, INFINITY);
   std::vector<int64_t> fcalls(nt, 0);
+  const double g_tol = opt->g_tol > 0 ? opt->g_tol : 1e-8;
+  // the starting points: x0, then nrestarts perturbed copies drawn from one generator start-major, then
+  // tree, then constant; caller-supplied starts (starts_in, [nrestarts][sum nconst]) replace the draws.
+  // Trees without constants or failing statically keep x0.
+  std::vector<std::vector<double>> starts(opt->nrestarts + 1, x0);
   std::mt19937_64 rng(opt->seed);
   std::normal_distribution<double> randn(0.0, 1.0);
-  const double g_tol = opt->g_tol > 0 ? opt->g_tol : 1e-8;
+  const bool f32 = P->dtype == SRHIP_F32;
+  for (int start = 1; start <= opt->nrestarts; ++start)
+    for (int32_t t : trees)
+      for (int64_t k = coff[t]; k < coff[t + 1]; ++k)
+        starts[start][k] = perturbed_start(x0[k], rng, randn, f32, starts_in ? starts_in + (int64_t)(start - 1) * nall + k : nullptr);
+  copy_starts_out(starts, starts_out);
   if (!trees.empty()) {
-    // the starting points: x0, then nrestarts perturbed copies drawn start-major, then tree, then
-    // constant (src/ConstantOptimization.jl:53-60: c * (1 + randn/2))
-    // Float32 trees perturb in T as the reference does (node.val * (T(1) + T(1//2) * randn(T))):
-    // a Float32 normal draw and Float32 arithmetic, the start rounded like the constant it replaces.
-    // Caller-supplied starts (starts_in, [nrestarts][sum nconst]) replace the draws; a Float32
-    // program rounds them to Float32.  Trees without constants or failing statically keep x0.
-    std::vector<std::vector<double>> starts(opt->nrestarts + 1, x0);
-    const bool f32 = P->dtype == SRHIP_F32;
-    const int64_t nall = (int64_t)x0.size();
-    for (int start = 1; start <= opt->nrestarts; ++start)
-      for (int32_t t : trees)
-        for (int64_t k = coff[t]; k < coff[t + 1]; ++k) {
-          double xs;
-          if (starts_in) {
-            xs = starts_in[(int64_t)(start - 1) * nall + k];
-          } else if (f32) {
-            const float r = (float)randn(rng);
-            xs = (double)((float)x0[k] * (1.0f + 0.5f * r));
-          } else {
-            xs = x0[k] * (1.0 + 0.5 * randn(rng));
-          }
-          starts[start][k] = f32 ? (double)(float)xs : xs;
-        }
-    if (starts_out)
-      for (int start = 1; start <= opt->nrestarts; ++start)
-        std::copy(starts[start].begin(), starts[start].end(), starts_out + (int64_t)(start - 1) * nall);
     const double tb = now_s();
-    g_t_compile = g_t_eval = g_t_host = 0.0;
-    g_patch_scan_s = g_patch_copy_s = 0.0;
-    g_n_launch = 0;
     const char* te = getenv("SRHIP_OPTIM_TIMING");
-    g_stats_on = te && (*te == '2' || *te == '3');
-    g_launch_log = te && *te == '3';
-    for (int64_t& h : g_hist) h = 0;
-    g_nonfinite_trials = 0;
-    g_spec_launched = g_spec_used = 0;
-    for (auto& a : g_items)
-      for (auto& b : a) b[0] = b[1] = 0;
+    reset_optim_counters(te && (*te == '2' || *te == '3'), te && *te == '3');
     rc = optimize_split(ctx, ds, P, loss, v, trees, coff, opt->iterations, g_tol, starts, best_x, best_f, fcalls);
     if (g_stats_on)
       fprintf(stderr, "srhip optim (the caller's group: 1 of SRHIP_OPTIM_SPLIT groups): launches by active trees: "
@@ -1397,36 +1384,18 @@ int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srh
               1e3 * (now_s() - tb), (long long)g_n_launch, 1e3 * g_t_eval, 1e3 * g_t_compile, 1e3 * g_patch_scan_s,
               1e3 * g_patch_copy_s, 1e3 * g_t_host);
     if (rc) {
-      set_all_consts(*P, x0.data());
-      compile_program(*P);
-      upload_program(*P);
+      restore_constants(*P, x0);
       return rc;
     }
-  } else if (starts_out) {
-    for (int start = 1; start <= opt->nrestarts; ++start)
-      std::copy(x0.begin(), x0.end(), starts_out + (int64_t)(start - 1) * (int64_t)x0.size());
   }
-  // accept where the best minimum beats the baseline (:70-78)
-  std::vector<double> final_x = x0;
-  for (int32_t t = 0; t < nt; ++t) {
-    const bool better = best_f[t] < base[t];
-    out_improved[t] = better ? 1 : 0;
-    if (better)
-      for (int64_t k = coff[t]; k < coff[t + 1]; ++k) final_x[k] = best_x[k];
-  }
-  set_all_consts(*P, final_x.data());
-  rc = compile_program(*P);
-  if (rc) return rc;
-  rc = upload_program(*P);
+  const std::vector<double> final_x = accept_against_baseline(x0, coff, best_x, best_f, base, out_improved);
+  rc = install_constants(*P, final_x);
   if (rc) return rc;
   // the loss of the returned trees, by the evaluator (the reference re-scores accepted members)
   std::vector<uint8_t> ok(nt);
   rc = run_eval(ctx, ds, P, MODE_LOSS, loss, idx, nidx, out_loss, nullptr, ok.data());
   if (rc) return rc;
-  // num_evals bookkeeping (src/ConstantOptimization.jl:51,65,79): the objective calls of every start
-  // (result.f_calls), plus one for the re-score of an accepted tree; 0 for a tree left alone
-  if (out_fcalls)
-    for (int32_t t = 0; t < nt; ++t) out_fcalls[t] = fcalls[t] + out_improved[t];
+  report_fcalls(fcalls, out_improved, out_fcalls);
   return SRHIP_OK;
 }
 
@@ -1441,23 +1410,6 @@ int srhip_optimize_constants(srhip_ctx* ctx, const srhip_dataset* ds, srhip_prog
 
 // ---- one row subset per tree: srhip_eval_loss_grad_rowsets / srhip_optimize_constants_rowsets ---------
 namespace {
-
-// srhip_eval_loss_rowsets' conventions and error texts
-int check_rowsets(const srhip_dataset* ds, int32_t nt, const int64_t* row_offsets, const int64_t* rows) {
-  if (!ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
-  if (row_offsets[0] != 0) return fail(SRHIP_ERR_INVALID, "row_offsets[0] must be 0");
-  for (int32_t t = 0; t < nt; ++t) {
-    if (row_offsets[t + 1] < row_offsets[t])
-      return fail(SRHIP_ERR_INVALID, "row_offsets[%d] = %lld < row_offsets[%d] = %lld", (int)t + 1,
-                  (long long)row_offsets[t + 1], (int)t, (long long)row_offsets[t]);
-    if (row_offsets[t + 1] == row_offsets[t]) return fail(SRHIP_ERR_INVALID, "tree %d has an empty row set", (int)t);
-    for (int64_t p = row_offsets[t]; p < row_offsets[t + 1]; ++p)
-      if (rows[p] < 0 || rows[p] >= ds->n)
-        return fail(SRHIP_ERR_INVALID, "tree %d: rows[%lld] (position %lld of its set) = %lld out of range [0, %lld)", (int)t,
-                    (long long)p, (long long)(p - row_offsets[t]), (long long)rows[p], (long long)ds->n);
-  }
-  return SRHIP_OK;
-}
 
 // The call's batch: the baseline through the rowsets evaluation (one launch; base_loss / base_ok), whose
 // per-set records (feature statistics, weight sums) are kept on the host, and every set a wave can stage
@@ -1524,13 +1476,6 @@ int make_rowset_batch(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P,
   return SRHIP_OK;
 }
 
-// tree t of P as a program of its own (the single-idx path of sets no wave can stage)
-int one_tree_program(srhip_ctx* ctx, const srhip_program* P, int32_t t, srhip_program** Q) {
-  const srhip_operators ops{(int32_t)P->binops.size(), (int32_t)P->unaops.size(), P->binops.data(), P->unaops.data()};
-  const int64_t offs[2] = {0, P->offsets[t + 1] - P->offsets[t]};
-  return srhip_program_create(ctx, P->dtype, P->nodes.data() + P->offsets[t], offs, 1, &ops, Q);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1561,7 +1506,7 @@ int srhip_eval_loss_grad_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_
       continue;
     }
     srhip_program* Q = nullptr;
-    rc = one_tree_program(ctx, P, t, &Q);
+    rc = subprogram(ctx, P, {t}, &Q);
     if (rc) return rc;
     rc = srhip_eval_loss_grad(ctx, ds, Q, loss, rows + row_offsets[t], row_offsets[t + 1] - row_offsets[t], out_loss + t,
                               out_grad + coff[t], out_ok + t);
@@ -1579,10 +1524,8 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
                                      const uint64_t* tree_seeds, const double* starts_in, double* starts_out,
                                      double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
   if (!row_offsets || !rows || !opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
-  if (opt->iterations < 0 || opt->nrestarts < 0) return fail(SRHIP_ERR_INVALID, "negative iterations / restarts");
-  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  int rc = check_optim_args(ctx, ds, P, loss, opt);
   if (rc) return rc;
-  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant optimisation needs Float32 / Float64");
   const int32_t nt = P->ntrees;
   rc = check_rowsets(ds, nt, row_offsets, rows);
   if (rc) return rc;
@@ -1604,46 +1547,25 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
   std::vector<double> best_x = x0, best_f(nt, INFINITY);
   std::vector<int64_t> fcalls(nt, 0);
   const double g_tol = opt->g_tol > 0 ? opt->g_tol : 1e-8;
-  const bool f32 = P->dtype == SRHIP_F32;
   // the starting points: x0, then nrestarts perturbed copies; tree t draws from a generator of its own
   // (tree_seeds[t], or opt->seed + t) start-major, then constant by constant -- the sequence the one-tree
-  // call draws (srhip_optimize_constants_starts), with its Float32 rule.  Trees without constants or
-  // failing statically keep x0.
+  // call draws (srhip_optimize_constants_starts).  Trees without constants or failing statically keep x0.
   std::vector<std::vector<double>> starts(opt->nrestarts + 1, x0);
+  const bool f32 = P->dtype == SRHIP_F32;
   auto tree_seed = [&](int32_t t) { return tree_seeds ? tree_seeds[t] : opt->seed + (uint64_t)t; };
   for (int32_t t = 0; t < nt; ++t) {
     if (!(P->info[t].nconst > 0 && !P->info[t].static_fail)) continue;
     std::mt19937_64 rng(tree_seed(t));
     std::normal_distribution<double> randn(0.0, 1.0);
     for (int start = 1; start <= opt->nrestarts; ++start)
-      for (int64_t k = coff[t]; k < coff[t + 1]; ++k) {
-        double xs;
-        if (starts_in) {
-          xs = starts_in[(int64_t)(start - 1) * nall + k];
-        } else if (f32) {
-          const float r = (float)randn(rng);
-          xs = (double)((float)x0[k] * (1.0f + 0.5f * r));
-        } else {
-          xs = x0[k] * (1.0 + 0.5 * randn(rng));
-        }
-        starts[start][k] = f32 ? (double)(float)xs : xs;
-      }
+      for (int64_t k = coff[t]; k < coff[t + 1]; ++k)
+        starts[start][k] = perturbed_start(x0[k], rng, randn, f32, starts_in ? starts_in + (int64_t)(start - 1) * nall + k : nullptr);
   }
-  if (starts_out)
-    for (int start = 1; start <= opt->nrestarts; ++start)
-      std::copy(starts[start].begin(), starts[start].end(), starts_out + (int64_t)(start - 1) * nall);
-  auto restore = [&]() {
-    set_all_consts(*P, x0.data());
-    compile_program(*P);
-    upload_program(*P);
-  };
+  copy_starts_out(starts, starts_out);
   if (!trees.empty()) {
     const View none{};
     const double tb = now_s();
-    g_t_compile = g_t_eval = g_t_host = 0.0;
-    g_patch_scan_s = g_patch_copy_s = 0.0;
-    g_n_launch = 0;
-    g_stats_on = g_launch_log = false;
+    reset_optim_counters(false, false);
     rc = bfgs_pipelined(ctx, ds, P, loss, none, trees, coff, opt->iterations, g_tol, starts, best_x, best_f, fcalls, &rb);
     const char* te = getenv("SRHIP_OPTIM_TIMING");  // the single-idx entry point's line, for this path
     if (te && *te && *te != '0')
@@ -1653,31 +1575,21 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
               1e3 * (now_s() - tb), (long long)g_n_launch, 1e3 * g_t_eval, 1e3 * g_t_compile, 1e3 * g_patch_scan_s,
               1e3 * g_patch_copy_s, 1e3 * g_t_host);
     if (rc) {
-      restore();
+      restore_constants(*P, x0);
       return rc;
     }
   }
-  // accept where the best minimum beats the baseline (:70-78)
-  std::vector<double> final_x = x0;
-  for (int32_t t = 0; t < nt; ++t) {
-    const bool better = best_f[t] < base[t];
-    out_improved[t] = better ? 1 : 0;
-    if (better)
-      for (int64_t k = coff[t]; k < coff[t + 1]; ++k) final_x[k] = best_x[k];
-  }
-  // the sets no wave can stage: the existing entry point on a one-tree program (its own view, baseline,
-  // optimiser run and acceptance), seeded with the tree's seed and given the tree's starts
+  std::vector<double> final_x = accept_against_baseline(x0, coff, best_x, best_f, base, out_improved);
+  // the sets no wave can stage: the single-idx entry point on a one-tree program (its own view, baseline,
+  // optimiser run and acceptance), seeded with the tree's seed and given the tree's starts.  (The tree is
+  // still at x0: the optimiser above moved only the staged trees' constants.)
   for (int32_t t : alone) {
     const int64_t nc = coff[t + 1] - coff[t];
-    std::vector<double> sin((size_t)opt->nrestarts * nc), cst;
+    std::vector<double> sin((size_t)opt->nrestarts * nc);
     for (int start = 1; start <= opt->nrestarts; ++start)
       for (int64_t k = 0; k < nc; ++k) sin[(size_t)(start - 1) * nc + k] = starts[start][coff[t] + k];
     srhip_program* Q = nullptr;
-    const srhip_operators ops{(int32_t)P->binops.size(), (int32_t)P->unaops.size(), P->binops.data(), P->unaops.data()};
-    // (the tree at x0: the optimiser above moved only the staged trees' constants)
-    std::vector<srhip_node> nd(P->nodes.begin() + P->offsets[t], P->nodes.begin() + P->offsets[t + 1]);
-    const int64_t offs[2] = {0, (int64_t)nd.size()};
-    rc = srhip_program_create(ctx, P->dtype, nd.data(), offs, 1, &ops, &Q);
+    rc = subprogram(ctx, P, {t}, &Q);
     if (rc == SRHIP_OK) {
       srhip_optim_options o1 = *opt;
       o1.seed = tree_seed(t);
@@ -1687,8 +1599,8 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
       rc = srhip_optimize_constants_starts(ctx, ds, Q, loss, rows + row_offsets[t], row_offsets[t + 1] - row_offsets[t], &o1,
                                            opt->nrestarts > 0 ? sin.data() : nullptr, nullptr, &l1, &imp, &fc);
       if (rc == SRHIP_OK) {
-        get_consts_rec(Q->nodes.data(), 0, cst);
-        for (int64_t k = 0; k < nc; ++k) final_x[coff[t] + k] = cst[k];
+        double* cst = final_x.data() + coff[t];
+        get_consts(Q->nodes.data(), 0, cst);
         out_improved[t] = imp;
         fcalls[t] = fc - imp;
       }
@@ -1696,21 +1608,17 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
     }
     if (rc) {
       const std::string msg = last_error();
-      restore();
+      restore_constants(*P, x0);
       return fail(rc, "%s", msg.c_str());
     }
   }
-  set_all_consts(*P, final_x.data());
-  rc = compile_program(*P);
-  if (rc) return rc;
-  rc = upload_program(*P);
+  rc = install_constants(*P, final_x);
   if (rc) return rc;
   // the loss of the returned trees, by the evaluator (the reference re-scores accepted members): one launch
   std::vector<uint8_t> ok(nt);
   rc = srhip_eval_loss_rowsets(ctx, ds, P, loss, row_offsets, rows, out_loss, ok.data());
   if (rc) return rc;
-  if (out_fcalls)
-    for (int32_t t = 0; t < nt; ++t) out_fcalls[t] = fcalls[t] + out_improved[t];
+  report_fcalls(fcalls, out_improved, out_fcalls);
   return SRHIP_OK;
 }
 

@@ -251,6 +251,62 @@ def test_optimizer_parity_with_the_one_tree_loop(ctx, dtype):
     assert again == got
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_one_call_crosses_every_kind_of_tree(ctx, dtype):
+    """One optimize_constants_rowsets call whose program holds every kind of tree the call's shared steps
+    (starts, acceptance, the one-tree path, install, re-score, fcalls) treat differently: staged sets (one
+    row, a sub-tile set, two blocks; BFGS and Newton), a set over every cap (2049 rows: the one-tree
+    path), a tree without constants and a tree that fails statically (a non-finite constant leaf).
+    Constants, loss, improved and fcalls equal, bit for bit, the per-tree optimize_constants calls with
+    the same seeds and starts."""
+    sr = _sr()
+    opts = sr.Options(binary_operators=("+", "-", "*", "/"), unary_operators=("cos", "exp"))
+    N_ = sr.Node
+    n = 4096
+    rng = np.random.default_rng(41)
+    X = rng.standard_normal((5, n)).astype(dtype)
+    y = (np.cos(1.3 * X[1]) * 2.0 + X[0] * 0.7 - 0.3).astype(dtype)
+    trees = [N_(val=0.5) * N_("x1") + N_(val=0.1),                                        # BFGS, staged
+             N_("cos", N_(val=1.1) * N_("x2")),                                           # Newton, over every cap
+             N_("x1") + N_("x3"),                                                         # no constants
+             N_("x1") * N_(val=np.inf),                                                   # fails statically
+             N_("cos", N_(val=1.2) * N_("x2")) * N_(val=1.5) + N_(val=0.6) * N_("x1") - N_(val=0.2),  # BFGS, two blocks
+             N_(val=0.3) * N_("x5")]                                                      # Newton, one row
+    lens = [50, 2049, 50, 50, 257, 1]
+    nt = len(trees)
+    nodes, offs = sr.flatten(trees, opts, dtype)
+    idxs = [rng.integers(0, n, size=m) for m in lens]
+    seeds = [int(s) for s in rng.integers(0, 2 ** 63 - 1, size=nt)]
+    ds = sr.DeviceDataset(ctx, X, y)
+    loss = sr.L2DistLoss()
+    kw = dict(iterations=3, nrestarts=1)
+    want = _optim_loop(sr, ctx, ds, nodes, offs, opts, dtype, loss, idxs, seeds, range(nt), **kw)
+    prog = sr.Program(ctx, nodes, offs, opts, dtype)
+    nconst = prog.num_constants()
+    assert list(nconst) == [2, 1, 0, 1, 4, 1]
+    got, starts = _optim_rowsets(prog, ds, loss, idxs, seeds, **kw)
+    prog.close()
+    for t in range(nt):
+        assert got[t] == want[t], (t, lens[t], got[t][:3], want[t][:3])
+    # every kind did what it is there for: the optimised trees improved, the other two were left alone
+    assert all(got[t][1] and got[t][2] > 0 for t in (0, 1, 4)), [got[t][1:3] for t in range(nt)]
+    assert all(got[t][2] == 0 and not got[t][1] for t in (2, 3))
+    assert got[3][0] == _bits(np.array([np.inf]))[0] and got[3][3] == _bits(np.array([np.inf])).tolist()
+    # the same starts given to both sides explicitly, other seeds: the same bits again
+    co = np.concatenate([[0], np.cumsum(nconst)]).astype(int)
+    want2 = {}
+    for t in range(nt):
+        p = _one_tree(sr, ctx, nodes, offs, t, opts, dtype)
+        l, imp, fc = p.optimize_constants(ds, loss, idx=idxs[t], seed=seeds[t] ^ 0x33, starts=starts[:, co[t]:co[t + 1]], **kw)
+        want2[t] = (_bits(l)[0], bool(imp[0]), int(fc[0]), _bits(p.get_constants()[0]).tolist())
+        p.close()
+    prog = sr.Program(ctx, nodes, offs, opts, dtype)
+    again, _ = _optim_rowsets(prog, ds, loss, idxs, [s ^ 0x5A5A for s in seeds], starts=starts, **kw)
+    prog.close()
+    assert again == got
+    assert {t: again[t][:4] for t in range(nt)} == want2
+
+
 @pytest.mark.parametrize("kind_name,args", [("HuberLoss", (0.7,)), ("LogitMarginLoss", ())])
 def test_loss_kinds(ctx, kind_name, args):
     sr = _sr()
