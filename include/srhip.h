@@ -402,6 +402,10 @@ double srhip_last_kernel_ms(const srhip_ctx* ctx);
  * rows), out[1] nominal node-rows (every live tree on every row), out[2] evaluated operator-node
  * rows, out[3] evaluated tree-rows. */
 int srhip_last_work(const srhip_ctx* ctx, int64_t out[4]);
+/* Launches of the interpreter's hot form on this context so far (the persistent main
+ * launch of the wide Float32 loss kernel with its per-slot records); < 0 for a null context.  The
+ * tests' way to see which form evaluated a population. */
+int64_t srhip_hot_form_launches(const srhip_ctx* ctx);
 /* Per-program work counters: sum over trees of count_nodes / operator nodes. */
 int srhip_program_stats(const srhip_program* prog, int64_t* total_nodes, int64_t* total_opnodes,
                         int32_t* max_stack);

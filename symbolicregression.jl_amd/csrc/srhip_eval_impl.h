@@ -176,8 +176,10 @@ __device__ __attribute__((always_inline)) inline void load_rows(const T* base, i
 
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const __attribute__((address_space(4))) Ins CIns;  // constant address space: scalar loads
+typedef const __attribute__((address_space(4))) SlotRec CSlotRec;
 #else
 typedef const Ins CIns;
+typedef const SlotRec CSlotRec;
 #endif
 
 template <typename T> __device__ __attribute__((always_inline)) inline T imm_as(uint64_t bits) {
@@ -1161,6 +1163,28 @@ __device__ __attribute__((always_inline)) inline void derive_columns_tiles(const
   __syncthreads();
 }
 
+// A kernel-argument field read again from the kernarg segment at the point of use (hot form): one
+// scalar load there instead of a scalar register -- past the SGPR budget, a vector lane moved by
+// v_readlane / v_writelane -- held across the dispatch loop.  EvalArgs is the kernel's only argument
+// (offset 0 of the segment).
+template <typename F>
+__device__ __attribute__((always_inline)) inline F karg_reload(uint32_t off) {
+  asm volatile("" : "+s"(off));  // (opaque: the load stays where it is written)
+  typedef const __attribute__((address_space(4))) unsigned char CB;
+  return *reinterpret_cast<const __attribute__((address_space(4))) F*>((CB*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
+// Hot form: a failed tree's loss chunks [c0, c1) of its row block (NaN: never read, the loss of a
+// failed tree is L(Inf)) and, with flag, its failure mark.  Out of line: the path is rare, and inline
+// its lane test merged into the tile loop's exit test and its counters stayed live through the loop.
+template <typename L>
+__device__ __attribute__((noinline)) void mark_failed(L* lslab, int c0, int c1, int32_t* flag, int32_t epoch) {
+  if (__builtin_amdgcn_inverse_ballot_w64(1ull << WAVE_LAST)) {
+    for (int c = c0; c < c1; ++c) lslab[c] = (L)NAN;
+    if (flag) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+#define SRHIP_KARG(f) (HOT ? karg_reload<decltype(EvalArgs::f)>((uint32_t)offsetof(EvalArgs, f)) : p.f)
+
 // ------------------------------------------------------------------------------------------------
 // The interpreter kernel.
 //   grid.x = row blocks (RB rows each), grid.y = tree groups; block = WAVES wavefronts.
@@ -1173,15 +1197,47 @@ __device__ __attribute__((always_inline)) inline void derive_columns_tiles(const
 // interleaved groups): the group is the order slots whose unit slot % gstride lies in
 // [gslice, gslice + gw) -- tree index ti is slot (ti / gw) * gstride + gslice + ti % gw, ascending, so
 // still in descending cost -- an interleaved gw/gstride of the population.
-template <typename T, int R, int K, int MODE, bool XLDS>
+//
+// FORM_HOT (the wide Float32 loss kernel's persistent main launch, where a C2 step spends 90 % of its
+// time): tile claims, the fused single-block records, grid grouping / interleaving, the diagnostic
+// stops and the device-listed precise fields are compile-time off, so their code and their scalar
+// live ranges are gone from the tree loop, and a tree's (tree, pc0, derived-column mask) come in
+// one scalar load of its order slot's record (EvalArgs::recs) instead of three dependent vector
+// loads.  Same arithmetic, same slab entries: every other launch keeps FORM_GENERAL.
+template <typename T, int R, int K, int MODE, bool XLDS, int FORM = FORM_GENERAL>
 __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs& p, unsigned char* smem, const int rb,
                                                                  const int gy, const int gslice = 0,
                                                                  const int gstride = 1, const int gw = 1) {
+  constexpr bool HOT = FORM == FORM_HOT;
+  static_assert(!HOT || (MODE == MODE_LOSS && XLDS && !kIsInt<T>), "the hot form is a staged loss launch");
   constexpr int WAVES = eval_waves(R, K);
   using O = OpsT<T>;
   using CT = typename Chk<T>::type;
   constexpr int TILE = 64 * R;
   const int lane = tid_x() & 63;  // (opaque: rematerialised instead of spilled across the block loop)
+  // the lane that holds a wave fold's result.  Hot form: the predicate is a constant execution mask
+  // (waves are always whole), not a compare whose 64-bit result is kept across the dispatch loop
+  auto last_lane = [&]() -> bool {
+    if constexpr (HOT) return __builtin_amdgcn_inverse_ballot_w64(1ull << WAVE_LAST);
+    else return lane == WAVE_LAST;
+  };
+  // Hot form: the launch's flags in one scalar word, decoded where they are tested (scalar bit tests).
+  // Left as they are, each test's 64-bit result is made once per launch and kept -- in vector lanes --
+  // across the dispatch loop: loss kind | weighted << 8 | early exit << 9
+  [[maybe_unused]] uint32_t hot_flags = 0;
+  if constexpr (HOT) {
+    hot_flags = ((uint32_t)p.loss_kind & 0xffu) | (p.weighted ? 0x100u : 0u) | (p.early_exit ? 0x200u : 0u);
+    asm volatile("" : "+s"(hot_flags));
+  }
+  auto flags_now = [&]() -> uint32_t {
+    uint32_t f = hot_flags;
+    asm volatile("" : "+s"(f));
+    return f;
+  };
+  auto early_exit_on = [&]() -> bool {
+    if constexpr (HOT) return (flags_now() & 0x200u) != 0;
+    else return p.early_exit != 0;
+  };
   const int64_t row_base = (int64_t)rb * p.rb_rows;
   const int ntiles = p.rb_rows / TILE;
   // valid rows of this block, block-relative (<= rb_rows): the tile loop's uniform row tests are
@@ -1230,9 +1286,11 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
   constexpr int FLAG_SNAP = 2048;
   constexpr bool SNAP = MODE == MODE_LOSS && !kIsInt<T>;
   __shared__ uint8_t failed_snap[SNAP ? FLAG_SNAP : 1];
-  const int gb0 = p.group_off ? p.group_off[gy] : gy * p.trees_per_group;
+  // (hot form: the one group is the whole population)
+  const int gb0 = HOT ? 0 : (p.group_off ? p.group_off[gy] : gy * p.trees_per_group);
   const int snap_base = gb0 + gslice;
   const int snap_n = gstride > 1 ? tail_units_count(p.ntrees, gstride, gslice, gw)
+                     : HOT       ? p.ntrees
                                  : (p.group_off ? p.group_off[gy + 1] - gb0 : min(p.trees_per_group, p.ntrees - gb0));
   if constexpr (SNAP) {
     if (p.early_exit)
@@ -1245,12 +1303,13 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
   __shared__ CT dchk[DERIVED ? DERIVE_MAX : 1];
   if constexpr (DERIVED) {
     if (p.nd > 0) {
-      if (p.persistent) derive_columns_tiles<T, R>(p, reinterpret_cast<T*>(smem), p.rb_rows, dchk);
+      if (HOT || p.persistent) derive_columns_tiles<T, R>(p, reinterpret_cast<T*>(smem), p.rb_rows, dchk);
       else derive_columns<T>(p, reinterpret_cast<T*>(smem), p.rb_rows, dchk);
     }
   }
   KMARK(0, 2);
-  if (p.debug_stop == 2) return;  // (diagnostic runs are never persistent)
+  if constexpr (!HOT)
+    if (p.debug_stop == 2) return;  // (diagnostic runs are never persistent)
 
   // tree group of this workgroup: uniform, or the host's tail-shaped sizes (group_off)
   const int group_base = __builtin_amdgcn_readfirstlane(snap_base);
@@ -1275,20 +1334,47 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
   // at a time, so the two tiles of a row block's costliest tree run on two waves at once; the check
   // statistic and the row count then combine by atomics (max of non-negative float bits; NaN bits
   // order above every finite and infinite value), each loss chunk is still written by one wave
-  const bool tile_claims = p.tile_claims != 0 && TILE == (sizeof(T) == 8 ? LOSS_CHUNK_8B : LOSS_CHUNK_4B);
+  const bool tile_claims = !HOT && p.tile_claims != 0 && TILE == (sizeof(T) == 8 ? LOSS_CHUNK_8B : LOSS_CHUNK_4B);
+  const bool fused = !HOT && p.fused != 0;
   const int nclaims = tile_claims ? group_n * ntiles : group_n;
   for (int cl = wave; cl < nclaims;) {
     const int ti = tile_claims ? cl / ntiles : cl;
     const int tile0 = tile_claims ? cl - ti * ntiles : 0, tile_end = tile_claims ? tile0 + 1 : ntiles;
     KMARK(8 + wave, 11);
-    const int slot = group_base + (gw > 1 ? ti / gw * gstride + ti % gw : ti * gstride);  // order slot (uniform)
-    const int tree = __builtin_amdgcn_readfirstlane(p.order[slot]);
-    const int pc0 = __builtin_amdgcn_readfirstlane(p.prog_off[tree]);
+    int gw_now = gw;
+    if constexpr (HOT) asm volatile("" : "+s"(gw_now));  // (the width is tested here, not once per block and kept)
+    // (... the division by the block's own gw: its reciprocal is made once per block)
+    const int slot = group_base + (gw_now > 1 ? ti / gw * gstride + ti % gw : ti * gstride);  // order slot (uniform)
+    int tree, pc0;
+    [[maybe_unused]] uint64_t rec_mask = 0;
+    [[maybe_unused]] int snap_failed = 0;
+    if constexpr (HOT) {
+      // the slot's record through the constant address space, uniform index: one s_load_dwordx4
+      const CSlotRec* recs = (const CSlotRec*)(uintptr_t)p.recs;
+      const SlotRec rec = recs[slot];
+      // ... and the tree's failure mark, read without a branch (used only under early_exit with
+      // ti < FLAG_SNAP) so that both are in flight under one wait
+      snap_failed = failed_snap[min(ti, FLAG_SNAP - 1)];
+      // (rec.tree is not used by this form, which writes its slabs by slot; it passes through the asm
+      // with the others so that the record stays one s_load_dwordx4 -- without it the load splits
+      // into a dwordx2 and a dword and the failure mark's read falls behind their wait)
+      uint32_t r0 = rec.tree, r1 = rec.pc0, r2 = rec.dmask_lo, r3 = rec.dmask_hi;
+      // (opaque: with the loaded words visible to it, the allocator moved the accumulator off v0-v15
+      // and spilled the stack registers around every out-of-line operator call)
+      asm volatile("" : "+s"(r0), "+s"(r1), "+s"(r2), "+s"(r3));
+      tree = (int)r0;
+      pc0 = (int)r1;
+      rec_mask = ((uint64_t)r3 << 32) | r2;
+    } else {
+      tree = __builtin_amdgcn_readfirstlane(p.order[slot]);
+      pc0 = __builtin_amdgcn_readfirstlane(p.prog_off[tree]);
+    }
     const int max_steps = __builtin_amdgcn_readfirstlane(p.max_steps);
     KDBG("[k] ti=%d tree=%d pc0=%d group_n=%d\n", ti, tree, pc0, group_n);
     KMARK(0, 3);
     KMARK(1, tree);
-    if (p.debug_stop == 3) break;  // (diagnostic) skip the trees; a continue would not claim the next one
+    if constexpr (!HOT)
+      if (p.debug_stop == 3) break;  // (diagnostic) skip the trees; a continue would not claim the next one
 
     if constexpr (MODE == MODE_PRECISE) {
       // device-listed trees: this wave owns the (tree, row block) entries, zeroed before accumulating
@@ -1306,14 +1392,22 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
     // another row block already saw this tree fail in this launch: nothing here can change its
     // result (did_succeed = false, loss L(Inf)); NaN partials and check statistic stand in
     bool failed = false;
-    if constexpr (SNAP) {
-      if (p.early_exit && ti < FLAG_SNAP) failed = __builtin_amdgcn_readfirstlane(failed_snap[ti]) != 0;
+    if constexpr (HOT) {
+      failed = early_exit_on() && ti < FLAG_SNAP && __builtin_amdgcn_readfirstlane(snap_failed) != 0;
+    } else if constexpr (SNAP) {
+      if (early_exit_on() && ti < FLAG_SNAP) failed = __builtin_amdgcn_readfirstlane(failed_snap[ti]) != 0;
     }
     if constexpr (DERIVED) {
-      if (p.nd > 0) {  // check statistics of the derived columns this tree reads
-        uint64_t msk = p.dmask[tree];
-        msk = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(msk >> 32)) << 32) |
-              (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)msk);
+      if (HOT || p.nd > 0) {  // check statistics of the derived columns this tree reads (hot form: no
+                              // columns, empty masks)
+        uint64_t msk;
+        if constexpr (HOT) {
+          msk = rec_mask;
+        } else {
+          msk = p.dmask[tree];
+          msk = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(msk >> 32)) << 32) |
+                (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)msk);
+        }
         while (msk) {
           const int d = __builtin_ctzll(msk);
           msk &= msk - 1;
@@ -1325,17 +1419,51 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
     // loss slab layout [row block][order slot][chunk of the block] (p.cpb chunks per block): a
     // workgroup's partials are one contiguous range (its group's slots), so L2 lines fill before
     // write-back
-    LAccT<T>* lslab = reinterpret_cast<LAccT<T>*>(p.slab_loss) +
-                      ((int64_t)rb * p.ntrees + slot) * __builtin_amdgcn_readfirstlane(p.cpb);
+    // (hot form: the one per-tree scalar is the 32-bit slab index of (row block, slot) -- the host
+    // launches the form only when every slab index fits -- and the slab bases, cpb, the failure
+    // flags and the epoch are read from the kernarg segment where they are used)
+    [[maybe_unused]] const int sidx = HOT ? rb * p.ntrees + slot : 0;
+    [[maybe_unused]] LAccT<T>* const lslab_gen =
+        HOT ? nullptr
+            : reinterpret_cast<LAccT<T>*>(p.slab_loss) +
+                  ((int64_t)rb * p.ntrees + slot) * __builtin_amdgcn_readfirstlane(p.cpb);
+    auto lslab_at = [&]() -> LAccT<T>* {
+      if constexpr (HOT) return reinterpret_cast<LAccT<T>*>(SRHIP_KARG(slab_loss)) + sidx * SRHIP_KARG(cpb);
+      else return lslab_gen;
+    };
     LAccT<T> csum = 0;  // fused launches: this lane's share of the tree's chunk sums
     int rows_done = 0;  // valid rows this wave evaluated the tree on (the launch's work count)
     if (failed) {
-      if (lane == WAVE_LAST)
+      if constexpr (HOT) {
+        mark_failed(lslab_at(), 0, SRHIP_KARG(cpb), nullptr, 0);
+      } else if (lane == WAVE_LAST) {
+        LAccT<T>* const lslab = lslab_at();
         for (int c = tile_claims ? tile0 : 0; c < (tile_claims ? tile_end : p.cpb); ++c) lslab[c] = (LAccT<T>)NAN;
+      }
       M = (CT)NAN;
       csum = (LAccT<T>)NAN;
     }
-    for (int tile = tile0; tile < (failed ? tile0 : tile_end); ++tile) {
+    // (hot form: the bound and the tree's code pointer are single opaque scalars -- left visible, the
+    // failed mask, the tile count, the pointer and the pointer plus one instruction were each kept
+    // across the dispatch loop in vector lanes and read back per tile)
+    [[maybe_unused]] int tile_stop = 0;
+    [[maybe_unused]] uint64_t prog_tree = 0;
+    if constexpr (HOT) {
+      tile_stop = failed ? tile0 : tile_end;
+      asm volatile("" : "+s"(tile_stop));
+      prog_tree = (uint64_t)(uintptr_t)(code + pc0);
+      asm volatile("" : "+s"(prog_tree));
+    }
+    auto prog_of_tile = [&]() -> const CIns* {
+      if constexpr (HOT) {
+        uint64_t pt = prog_tree;
+        asm volatile("" : "+s"(pt));  // (the first instruction's address plus one is made here, per tile)
+        return (const CIns*)(uintptr_t)pt;
+      } else {
+        return code + pc0;
+      }
+    };
+    for (int tile = tile0; tile < (HOT ? tile_stop : (failed ? tile0 : tile_end)); ++tile) {
       const int64_t row0 = row_base + (int64_t)tile * TILE;
       const int trel = tile * TILE;
       if (trel >= nrel) break;  // whole tile is padding
@@ -1355,11 +1483,13 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
 #endif
       // The program is read through the constant address space with a wave-uniform pc, so every
       // instruction is one s_load_dwordx4 (scalar cache), prefetched one instruction ahead.
-      const CIns* prog = code + pc0;
+      const CIns* prog = prog_of_tile();
       Ins nxt = prog[0];
       [[maybe_unused]] uint32_t pord = 0;  // MODE_PRECISE: operators executed so far (precise_hook)
       // bounded: a malformed program ends after max_steps instructions instead of hanging
-      for (int step = 0; step < max_steps; ++step) {
+      int steps_max = max_steps;
+      if constexpr (HOT) asm volatile("" : "+s"(steps_max));  // (the loop's entry test is made here, per tile)
+      for (int step = 0; step < steps_max; ++step) {
         const Ins ins = nxt;
         nxt = prog[step + 1];
         KDBG("[k]   tile=%d step=%d h=%u a=%u\n", tile, step, ins.h, ins.a);
@@ -1502,15 +1632,25 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
       KDBG("[k]   tile %d done\n", tile);
       KMARK(0, 4);
       if constexpr (MODE == MODE_LOSS) {
-        loss_tile<T, R>(p, A, ysrc + (int64_t)tile * TILE, wsrc + (int64_t)tile * TILE, lane, row0, trel + TILE <= nrel,
-                        lacc);
+        if constexpr (HOT) {
+          EvalArgs pl = p;  // (only the fields loss_tile reads survive)
+          const uint32_t f = flags_now();
+          pl.loss_kind = (int32_t)(f & 0xffu);
+          pl.weighted = (int32_t)((f >> 8) & 1u);
+          loss_tile<T, R>(pl, A, ysrc + (int64_t)tile * TILE, wsrc + (int64_t)tile * TILE, lane, row0,
+                          trel + TILE <= nrel, lacc);
+        } else {
+          loss_tile<T, R>(p, A, ysrc + (int64_t)tile * TILE, wsrc + (int64_t)tile * TILE, lane, row0,
+                          trel + TILE <= nrel, lacc);
+        }
         const bool flushed = (tile + 1) % TPC == 0 || trel + TILE >= nrel;
         const int ci0 = tile * CPT / TPC;  // the tile's (first) loss chunk
         if (flushed) {  // chunk(s) done (or last valid tile)
+          LAccT<T>* const lslab = lslab_at();
           UNR for (int c = 0; c < CPT; ++c) {
             const LAccT<T> s = wave_sum(lacc[c]);
-            if (lane == WAVE_LAST) lslab[ci0 + c] = s;
-            if (p.fused) {  // reduce_kernel's lane-strided accumulation: lane c % 64 adds chunk c
+            if (last_lane()) lslab[ci0 + c] = s;
+            if (fused) {  // reduce_kernel's lane-strided accumulation: lane c % 64 adds chunk c
               const LAccT<T> sb = __shfl(s, WAVE_LAST);
               if (lane == (ci0 + c) % 64) csum += sb;
             }
@@ -1523,9 +1663,14 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
           // fails every tree whose statistic is non-finite), so its remaining tiles in this row
           // block cannot change any result.  The unwritten loss chunks get NaN (never read: a failed
           // tree's loss is L(Inf)); M keeps the non-finite value the host sees.
-          if (p.early_exit && __builtin_amdgcn_ballot_w64(!(M < (CT)INFINITY)) != 0) {
+          if (early_exit_on() && __builtin_amdgcn_ballot_w64(!(M < (CT)INFINITY)) != 0) {
             csum = (LAccT<T>)NAN;
-            if (lane == WAVE_LAST) {
+            if constexpr (HOT) {
+              // (the slot from the slab index: nothing else needs it past the tree's set-up)
+              mark_failed(lslab_at(), ci0 + (flushed ? CPT : 0), SRHIP_KARG(cpb),
+                          SRHIP_KARG(fail_flag) + (sidx - rb * SRHIP_KARG(ntrees)), SRHIP_KARG(epoch));
+            } else if (lane == WAVE_LAST) {
+              LAccT<T>* const lslab = lslab_at();
               for (int c = ci0 + (flushed ? CPT : 0); c < (tile_claims ? tile_end : p.cpb); ++c)
                 lslab[c] = (LAccT<T>)NAN;
               __hip_atomic_store(p.fail_flag + slot, p.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1543,8 +1688,9 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
     // ---- wave reduction, one partial per (tree, row block) ----
     if constexpr (!kIsInt<T> && MODE != MODE_PRECISE) {
       M = wave_chk(M);
-      CT* chk_at = reinterpret_cast<CT*>(p.slab_chk) + (int64_t)rb * p.ntrees + slot;
-      if (lane == WAVE_LAST) {
+      CT* chk_at = HOT ? reinterpret_cast<CT*>(SRHIP_KARG(slab_chk)) + sidx
+                       : reinterpret_cast<CT*>(p.slab_chk) + (int64_t)rb * p.ntrees + slot;
+      if (last_lane()) {
         if constexpr (sizeof(CT) == 4) {
           if (tile_claims) atomicMax(reinterpret_cast<unsigned*>(chk_at), __builtin_bit_cast(unsigned, __builtin_fabsf(M) == __builtin_fabsf(M) ? __builtin_fabsf(M) : M));
           else *chk_at = M;
@@ -1553,12 +1699,14 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
         }
       }
     }
-    if (p.slab_rows && lane == WAVE_LAST) {
+    if constexpr (HOT) {
+      if (last_lane()) SRHIP_KARG(slab_rows)[sidx] = rows_done;
+    } else if (p.slab_rows && lane == WAVE_LAST) {
       if (tile_claims) atomicAdd(p.slab_rows + (int64_t)rb * p.ntrees + slot, rows_done);
       else p.slab_rows[(int64_t)rb * p.ntrees + slot] = rows_done;
     }
     if constexpr (MODE != MODE_PRECISE) {
-      if (p.fused) {  // the only row block: reduce_kernel's steps for this tree, same order, same bits
+      if (fused) {  // the only row block: reduce_kernel's steps for this tree, same order, same bits
         LAccT<T> s = csum;
         CT m = 0;
         if constexpr (!kIsInt<T>) {
@@ -1600,11 +1748,13 @@ __device__ __attribute__((always_inline)) inline void eval_block(const EvalArgs&
 //   MODE_LOSS: fused loss partial + check partial per (tree, row block) -> slabs
 //   MODE_PRED: prediction rows -> out_pred[tree][row], check partial -> slab
 // ------------------------------------------------------------------------------------------------
-template <typename T, int R, int K, int MODE, bool XLDS>
+template <typename T, int R, int K, int MODE, bool XLDS, int FORM = FORM_GENERAL>
 __global__ __launch_bounds__(64 * eval_waves(R, K)) void eval_kernel(EvalArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr bool HOT = FORM == FORM_HOT;  // persistent, whole-tree claims, no grid forms (eval_block)
   KMARK(0, 1);
-  if (p.debug_stop == 1) return;
+  if constexpr (!HOT)
+    if (p.debug_stop == 1) return;
   // items [0, nfull): whole row blocks block0 .. block0 + nfull - 1; then tail_shares items, the
   // equal shares of the remaining tail_blocks row blocks' units (srhip_tail_shares.h: the last
   // round of a launch ends on every workgroup at nearly the same time).  A share is one or two
@@ -1617,7 +1767,7 @@ __global__ __launch_bounds__(64 * eval_waves(R, K)) void eval_kernel(EvalArgs p)
     // its workgroups leave at once (the launch is enqueued whether or not the list holds a tree)
     if (p.dev_count && p.grid_interleave && __builtin_amdgcn_readfirstlane(*p.dev_count) <= (int)blockIdx.y) return;
   }
-  if (p.tile_claims && !p.persistent) {
+  if (!HOT && p.tile_claims && !p.persistent) {
     // the probe's combining entries start from zero (eval_block's first barrier orders these stores
     // before any wave's atomics); no memset launches before the probe.  Only this workgroup's waves
     // combine into its entries, and the later readers are later launches: a workgroup-scope release
@@ -1639,12 +1789,12 @@ __global__ __launch_bounds__(64 * eval_waves(R, K)) void eval_kernel(EvalArgs p)
   int next_block = 0, next_units = 0; // a claimed share's second part (units [0, next_units)), if pending
   for (int it = 0;; ++it) {
     int rb, gy = 0, gslice = 0, gstride = 1, gw = 1;
-    if (p.persistent && next_units > 0) {
+    if ((HOT || p.persistent) && next_units > 0) {
       rb = next_block;
       gstride = p.tail_slices;
       gw = next_units;
       next_units = 0;
-    } else if (p.persistent) {
+    } else if (HOT || p.persistent) {
       if (threadIdx.x == 0) claimed = atomicAdd(p.block_ctr, 1);
       __syncthreads();
       const int item = __builtin_amdgcn_readfirstlane(claimed);
@@ -1686,16 +1836,16 @@ __global__ __launch_bounds__(64 * eval_waves(R, K)) void eval_kernel(EvalArgs p)
         gy = blockIdx.y;
       }
     }
-    eval_block<T, R, K, MODE, XLDS>(p, smem, rb, gy, gslice, gstride, gw);
-    if (!p.persistent && !p.block_stride) break;
+    eval_block<T, R, K, MODE, XLDS, FORM>(p, smem, rb, gy, gslice, gstride, gw);
+    if (!HOT && !p.persistent && !p.block_stride) break;
     __syncthreads();  // every wave is done with this block's LDS (and has read `claimed`)
   }
 }
 
 // ---- launch helpers, instantiated by the per-variant translation units ----
-template <typename T, int R, int K, int MODE, bool XLDS>
+template <typename T, int R, int K, int MODE, bool XLDS, int FORM = FORM_GENERAL>
 inline hipError_t launch_eval_t(const EvalArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  auto kern = eval_kernel<T, R, K, MODE, XLDS>;
+  auto kern = eval_kernel<T, R, K, MODE, XLDS, FORM>;
   if (lds > 65536) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

@@ -1738,6 +1738,26 @@ std::vector<int32_t> make_order(const srhip_program& P, const std::vector<int32_
   return order;
 }
 
+// The hot form's slot records (SlotRec: what a wave reads per tree, in one scalar load) behind an
+// order and its group offsets: [order | goff | pad to 16 bytes | records], one upload.  The records
+// belong to the plan the order was made for: pc0 and the mask are the derived-column program's when
+// that plan evaluates it.  Returns the records' offset in int32 units.
+static int append_slot_records(const srhip_program& P, std::vector<int32_t>& order, int nl, bool derived) {
+  while (order.size() % 4 != 0) order.push_back(0);
+  const int at = (int)order.size();
+  order.resize((size_t)at + 4 * (size_t)nl);
+  for (int sl = 0; sl < nl; ++sl) {
+    const int32_t t = order[sl];
+    const uint64_t m = derived ? P.dmask[t] : 0;
+    int32_t* r = order.data() + at + 4 * (size_t)sl;
+    r[0] = t;
+    r[1] = derived ? P.dprog_off[t] : P.prog_off[t];
+    r[2] = (int32_t)(uint32_t)m;
+    r[3] = (int32_t)(uint32_t)(m >> 32);
+  }
+  return at;
+}
+
 // ---- the did_succeed decision, from (possibly all-reduced) partials ----------------------------
 // Partials layout (the C ABI's srhip_eval_loss_partials): sums[2t] = sum of (w *) l over the rows,
 // sums[2t+1] = sum of w (unweighted: the row count); sums[2T + 2f] = feature f column sum (Float64
@@ -2203,16 +2223,18 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
   }
   const int nl = (int)live.size();
   const void* d_order;
+  int rec_at = -1;  // the plan's slot records behind the order (int32 units), if it has them
   // persistent launches: one group, the order globally by descending cost (the probe's uniform
   // groups of one tree per wave are consecutive slots of it)
   const std::vector<int32_t> goff = persistent ? std::vector<int32_t>{0, nl} : shape_groups(L, nl, ctx->num_cu);
   {
     std::lock_guard<std::mutex> g(P->ord_mu);
     if (P->upload_pending || P->ord_key[0] != L.groups || P->ord_key[1] != L.tpg || P->ord_key[2] != (int)use_d ||
-        P->ord_goff != goff) {
+        P->ord_goff != goff || (persistent && P->ord_recs < 0)) {
       std::vector<int32_t>& order = P->ord_host;  // lives in the program: the copy below is asynchronous
       order = make_order(*P, live, goff, use_d);
       order.insert(order.end(), goff.begin(), goff.end());  // the group offsets follow the order
+      P->ord_recs = persistent ? append_slot_records(*P, order, nl, use_d) : -1;  // ... and the slot records
       if (P->upload_pending) {  // deferred program upload: program and order in one copy
         const size_t base = P->blob_off[6], bytes = order.size() * sizeof(int32_t);
         P->blob.resize(base + bytes);
@@ -2234,6 +2256,7 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
       P->ord_goff = goff;
     }
     d_order = P->ord_dev;
+    rec_at = P->ord_recs;
   }
   const int nch = (int)((v.m + loss_chunk(dtype) - 1) / loss_chunk(dtype));
   const int cpb = L.rb_rows / loss_chunk(dtype);  // loss chunks per row block (row blocks are whole chunks)
@@ -2409,7 +2432,14 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
       }
     }
     J.expect_items = nmain - a.tail_blocks + a.tail_shares;
+    // the hot form (FORM_HOT; launch_eval_f32w takes it when the launch carries records): this launch of
+    // the wide Float32 loss kernel, slab results, no diagnostics, every slab index in 32 bits.
+    // SRHIP_NO_HOT_FORM=1: the general form (read per launch)
+    if (R == R_F32_WIDE && K == 2 && rec_at >= 0 && !a.fused && a.slab_rows && !a.dbg && a.debug_stop == 0 &&
+        a.loss_kind >= 0 && a.loss_kind < 256 && (int64_t)nl * L.nrb * cpb < ((int64_t)1 << 31) && !env_flag("SRHIP_NO_HOT_FORM"))
+      a.recs = (const SlotRec*)((const int32_t*)d_order + rec_at);
     HIP_TRY(launch_eval(dtype, a, R, K, mode, true, dim3(wgs, 1), L.lds, ctx->stream));
+    if (a.recs) ++ctx->hot_launches;  // (counted once the launch is enqueued)
   } else {
     HIP_TRY(launch_eval(dtype, a, R, K, mode, L.xlds, grid, L.lds, ctx->stream));
   }
@@ -2947,6 +2977,7 @@ static void plan_persistent_order(const srhip_ctx* ctx, srhip_program& P) {
   std::lock_guard<std::mutex> g(P.ord_mu);
   P.ord_host = make_order(P, live, goff, use_d);
   P.ord_host.insert(P.ord_host.end(), goff.begin(), goff.end());
+  P.ord_recs = append_slot_records(P, P.ord_host, nl, use_d);
   P.ord_key[0] = 1;
   P.ord_key[1] = nl;
   P.ord_key[2] = (int)use_d;
@@ -3600,6 +3631,8 @@ int srhip_last_work(const srhip_ctx* ctx, int64_t* out) {
   for (int i = 0; i < 4; ++i) out[i] = ctx->work[i];
   return SRHIP_OK;
 }
+
+int64_t srhip_hot_form_launches(const srhip_ctx* ctx) { return ctx ? ctx->hot_launches : -1; }
 
 int srhip_program_stats(const srhip_program* P, int64_t* total_nodes, int64_t* total_opnodes, int32_t* max_stack) {
   if (!P) return fail(SRHIP_ERR_INVALID, "null program");

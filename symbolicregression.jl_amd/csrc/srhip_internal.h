@@ -224,6 +224,7 @@ struct srhip_ctx {
   // evaluated node-rows, nominal node-rows (every live tree on every row), evaluated operator-node
   // rows, evaluated tree-rows
   int64_t work[4] = {0, 0, 0, 0};
+  int64_t hot_launches = 0;  // hot-form launches so far (srhip_hot_form_launches)
   // a second context on the same device (own stream and buffers), created on first use by the
   // constant optimiser, which runs half of the population on it from a second host thread
   std::vector<srhip_ctx*> aux;
@@ -290,6 +291,7 @@ struct srhip_program {
   mutable std::vector<int32_t> ord_goff;  // group offsets of that plan (appended to d_order)
   mutable std::vector<int32_t> ord_host;  // the uploaded order (kept alive: its copy is asynchronous)
   mutable const void* ord_dev = nullptr;  // where it lives on the device (d_order, or inside d_prog)
+  mutable int ord_recs = -1;  // the plan's slot records (SlotRec) behind order and offsets, in int32 units; -1: none
   mutable srhip::PoolBuf d_order;
   // gradient program (constants not folded, constant leaves carry their get_constants index);
   // compiled on first use by the constant-gradient path

@@ -48,6 +48,21 @@ struct FeatStat {
 constexpr int FEAT_STAT_BLOCKS = 64;
 inline size_t feature_stats_scratch(int64_t nfeat) { return (size_t)(nfeat < 1 ? 1 : nfeat) * (1 + FEAT_STAT_BLOCKS); }
 
+// Forms of the interpreter kernel (eval_kernel's last template argument).  FORM_HOT: the persistent
+// main launch of the wide Float32 loss kernel -- whole-tree claims over staged row blocks, slab
+// results only; its launch carries EvalArgs::recs.  Everything else runs FORM_GENERAL.
+constexpr int FORM_GENERAL = 0, FORM_HOT = 1;
+// What a hot-form wave reads per tree, by order slot, in one 16-byte scalar load.  Built by the host
+// with the launch order (the program of the launch: pc0 and the mask are the derived-column
+// program's when the launch uses it) and uploaded in the same copy.
+struct alignas(16) SlotRec {
+  int32_t tree;       // order[slot]
+  int32_t pc0;        // prog_off[tree]
+  uint32_t dmask_lo;  // dmask[tree] (0 without derived columns)
+  uint32_t dmask_hi;
+};
+static_assert(sizeof(SlotRec) == 16, "one s_load_dwordx4");
+
 struct EvalArgs {
   const Ins* code;          // all trees' bytecode
   const int32_t* prog_off;  // [ntrees] first instruction of each tree
@@ -116,6 +131,7 @@ struct EvalArgs {
                             // sums instead of adding to them (no dependent load per operator)
   int32_t* slab_rows;       // [nrb][ntrees] valid rows each (row block, order slot) evaluated, or nullptr
   int64_t* fused_rows;      // fused launches: [program trees] rows evaluated (coherent pinned host), or nullptr
+  const SlotRec* recs;      // [ntrees] by order slot: FORM_HOT launches (else nullptr)
 };
 
 int rows_per_lane(int dtype);

@@ -132,6 +132,7 @@ SIGNATURES = {
     "srhip_eval_loss_sharded": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, _vp, _vp]),
     "srhip_last_kernel_ms": (_dbl, [_vp]),
     "srhip_last_work": (ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
+    "srhip_hot_form_launches": (ctypes.c_int64, [_vp]),
     "srhip_program_stats": (ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                            ctypes.POINTER(_i32)]),
     "srhip_program_derived": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), _vp, _i32]),

@@ -38,6 +38,10 @@ class Context:
         return {"node_rows": int(out[0]), "nominal_node_rows": int(out[1]), "opnode_rows": int(out[2]),
                 "tree_rows": int(out[3])}
 
+    def hot_form_launches(self) -> int:
+        """Launches of the interpreter's hot form on this context so far (srhip_hot_form_launches)."""
+        return int(self._lib.srhip_hot_form_launches(self.handle))
+
     def close(self):
         if self.handle:
             self._lib.srhip_ctx_destroy(self.handle)
