@@ -414,6 +414,21 @@ int srhip_program_stats(const srhip_program* prog, int64_t* total_nodes, int64_t
  * min(count, cap) entries as (device unary op << 16) | (feature - 1).  Set SRHIP_NO_DERIVE=1
  * before srhip_program_create to compile without them. */
 int srhip_program_derived(const srhip_program* prog, int32_t* count, uint32_t* spec, int32_t cap);
+/* The interpreter's instruction set, for tests and diagnostics (no device is needed).  Handler ids run
+ * from 0 to srhip_isa_handler_count() - 1; srhip_isa_handler_name writes an id's name ("END", "LOADF",
+ * "PUSHLC2", "SUB.SA3", "ADD.FC", "POW.AS0", "UN.erfc": operator, operand form, stack slot) into buf;
+ * srhip_isa_handler_ok returns 1 if the kernels of element type dtype implement the handler, 0 if not
+ * (Int32 has the ring operators and comparisons only), a negative value for arguments out of range. */
+int32_t srhip_isa_handler_count(void);
+int srhip_isa_handler_name(uint32_t h, char* buf, int32_t cap);
+int srhip_isa_handler_ok(uint32_t h, int dtype);
+/* The handler ids of one tree's evaluation program in execution order, its END included, as a launch
+ * runs them: after constant folding and the superinstruction pass, through the code cache.  derived
+ * != 0: the derived-column program (srhip_program_derived) when the program has one, which launches
+ * prefer; 0: the plain program.  *count receives the length; out (may be NULL) the first min(count,
+ * cap) ids.  A tree the host already decided as failed is its END alone. */
+int srhip_program_handlers(const srhip_program* prog, int32_t tree, int32_t derived, uint32_t* out, int32_t cap,
+                           int32_t* count);
 /* Process-wide counters of the per-tree code cache used by srhip_program_create (any argument may be
  * NULL): trees served from the cache, trees compiled, entries made (a tree gets an entry on its
  * second sighting; SRHIP_CODE_CACHE_EAGER=1: on its first). */

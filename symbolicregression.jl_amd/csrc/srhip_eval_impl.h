@@ -141,14 +141,9 @@ template <typename T>
 using OpsT = typename std::conditional<kIsInt<T>, IOps, FOps<typename std::conditional<kIsInt<T>, float, T>::type>>::type;
 
 // Which handlers exist for T (Int32 trees: ring ops and comparisons only).
-template <typename T> __device__ constexpr bool sb_ok(int sb) {
-  return !kIsInt<T> || sb != SB_DIV;
-}
-template <typename T> __device__ constexpr bool hb_ok(int) { return !kIsInt<T>; }
-template <typename T> __device__ constexpr bool un_ok(int u) {
-  return !kIsInt<T> || u == UN_NEG || u == UN_SQUARE || u == UN_CUBE || u == UN_ABS ||
-         u == UN_RELU || u == UN_SIGN;
-}
+template <typename T> __device__ constexpr bool sb_ok(int sb) { return isa_sb_ok(kIsInt<T>, sb); }
+template <typename T> __device__ constexpr bool hb_ok(int hb) { return isa_hb_ok(kIsInt<T>, hb); }
+template <typename T> __device__ constexpr bool un_ok(int u) { return isa_un_ok(kIsInt<T>, u); }
 
 // 16-byte vector of T
 template <typename T> struct Vec16;

@@ -3649,4 +3649,77 @@ int srhip_program_derived(const srhip_program* P, int32_t* count, uint32_t* spec
   return SRHIP_OK;
 }
 
+// ---- the interpreter's handler ids, by name and by program (no device) -----------------------------
+int32_t srhip_isa_handler_count(void) { return (int32_t)H_COUNT; }
+
+int srhip_isa_handler_name(uint32_t h, char* buf, int32_t cap) {
+  if (!buf || cap < 1) return fail(SRHIP_ERR_INVALID, "null or empty name buffer");
+  if (h >= H_COUNT) return fail(SRHIP_ERR_INVALID, "handler id %u out of range (< %u)", h, H_COUNT);
+  static const char* const spec_names[] = {
+#define X_(n, f) #n,
+      SRHIP_SPEC_BINOPS(X_)
+#undef X_
+  };
+  static const char* const heavy_names[] = {
+#define X_(n, f) #n,
+      SRHIP_HEAVY_BINOPS(X_)
+#undef X_
+  };
+  static const char* const un_names[] = {
+#define X_(n, f) #f,
+      SRHIP_UNOPS(X_)
+#undef X_
+  };
+  static const char* const slot_names[] = {"SLOADF", "SLOADC", "PUSH", "PUSHLF", "PUSHLC"};
+  static const char* const form_names[] = {"AF", "FA", "AC", "CA"};
+  static const char* const leaf_forms[] = {"FF", "FC", "CF"};
+  if (h == H_END) snprintf(buf, (size_t)cap, "END");
+  else if (h == H_LOADF) snprintf(buf, (size_t)cap, "LOADF");
+  else if (h == H_LOADC) snprintf(buf, (size_t)cap, "LOADC");
+  else if (h < H_BIN0) snprintf(buf, (size_t)cap, "%s%u", slot_names[(h - H_SLOADF0) / K_MAX], (h - H_SLOADF0) % K_MAX);
+  else if (h < H_HEAVY0) {
+    const char* op = spec_names[(h - H_BIN0) / SPEC_STRIDE];
+    const uint32_t form = (h - H_BIN0) % SPEC_STRIDE;
+    if (form < SPEC_SA0) snprintf(buf, (size_t)cap, "%s.%s", op, form_names[form]);
+    else if (form < SPEC_AS0) snprintf(buf, (size_t)cap, "%s.SA%u", op, form - SPEC_SA0);
+    else if (form < SPEC_FF) snprintf(buf, (size_t)cap, "%s.AS%u", op, form - SPEC_AS0);
+    else snprintf(buf, (size_t)cap, "%s.%s", op, leaf_forms[form - SPEC_FF]);
+  } else if (h < H_UN0) {
+    const char* op = heavy_names[(h - H_HEAVY0) / HEAVY_STRIDE];
+    const uint32_t form = (h - H_HEAVY0) % HEAVY_STRIDE;
+    snprintf(buf, (size_t)cap, "%s.%s%u", op, form < HEAVY_AS0 ? "SA" : "AS", form % K_MAX);
+  } else {
+    snprintf(buf, (size_t)cap, "UN.%s", un_names[h - H_UN0]);
+  }
+  return SRHIP_OK;
+}
+
+int srhip_isa_handler_ok(uint32_t h, int dtype) {
+  if (h >= H_COUNT || (dtype != SRHIP_F32 && dtype != SRHIP_F64 && dtype != SRHIP_I32)) return -1;
+  const bool is_int = dtype == SRHIP_I32;
+  if (h < H_BIN0) return 1;
+  if (h < H_HEAVY0) return isa_sb_ok(is_int, (int)((h - H_BIN0) / SPEC_STRIDE)) ? 1 : 0;
+  if (h < H_UN0) return isa_hb_ok(is_int, (int)((h - H_HEAVY0) / HEAVY_STRIDE)) ? 1 : 0;
+  return isa_un_ok(is_int, (int)(h - H_UN0)) ? 1 : 0;
+}
+
+int srhip_program_handlers(const srhip_program* P, int32_t tree, int32_t derived, uint32_t* out, int32_t cap,
+                           int32_t* count) {
+  if (!P || !count) return fail(SRHIP_ERR_INVALID, "null argument");
+  if (tree < 0 || tree >= P->ntrees) return fail(SRHIP_ERR_INVALID, "tree %d out of range (%d trees)", (int)tree, (int)P->ntrees);
+  const bool der = derived && !P->dspec.empty();
+  const std::vector<Ins>& code = der ? P->dcode : P->code;
+  size_t i = (size_t)(der ? P->dprog_off[tree] : P->prog_off[tree]);
+  int32_t n = 0;
+  for (; i < code.size(); ++i, ++n) {
+    if (out && n < cap) out[n] = code[i].h;
+    if (code[i].h == H_END) {
+      ++n;
+      break;
+    }
+  }
+  *count = n;
+  return SRHIP_OK;
+}
+
 }  // extern "C"

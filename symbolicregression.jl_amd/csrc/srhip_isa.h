@@ -58,6 +58,14 @@ constexpr bool un_cheap(int u) {
 // "Wide" unary operators (OCML bodies with ~100 live VGPRs): only the K = K_MAX variant has them.
 constexpr bool un_wide_op(int u) { return u == UN_ASIN || u == UN_ACOS || u == UN_ATANH_CLIP; }
 
+// Which operator handlers exist for an element type (Int32 trees: ring ops and comparisons only; the
+// interpreter's sb_ok / hb_ok / un_ok and the host's srhip_isa_handler_ok both read these).
+constexpr bool isa_sb_ok(bool is_int, int sb) { return !is_int || sb != SB_DIV; }
+constexpr bool isa_hb_ok(bool is_int, int) { return !is_int; }
+constexpr bool isa_un_ok(bool is_int, int u) {
+  return !is_int || u == UN_NEG || u == UN_SQUARE || u == UN_CUBE || u == UN_ABS || u == UN_RELU || u == UN_SIGN;
+}
+
 // Derived columns: a heavy unary operator applied directly to a feature leaf, U(X[f]), has the same
 // value in every tree of a population.  The host lists the (U, f) pairs a program uses at least
 // DERIVE_MIN_USES times; each workgroup computes them once for its rows into LDS columns after the

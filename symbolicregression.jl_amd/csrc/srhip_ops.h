@@ -67,7 +67,6 @@ SRHIP_HD float m_log(float x) { return srm_logf(x); }
 SRHIP_HD double m_log(double x) { return srm_log(x); }
 SRHIP_WRAP1(log2, log2)
 SRHIP_WRAP1(log10, log10)
-SRHIP_WRAP1(log1p, log1p)
 SRHIP_WRAP1(acosh, acosh)
 SRHIP_WRAP1(atanh, atanh)
 SRHIP_WRAP1(sinh, sinh)
@@ -81,9 +80,14 @@ SRHIP_WRAP1(erf, erf)
 SRHIP_WRAP1(erfc, erfc)
 SRHIP_WRAP1(tgamma, tgamma)
 SRHIP_WRAP1(exp2, exp2)
-SRHIP_WRAP1(expm1, expm1)
 SRHIP_WRAP1(cbrt, cbrt)
 #undef SRHIP_WRAP1
+// log1p and expm1 keep the sign of a zero argument (IEEE 754, glibc); the device's Float32 path returned
+// +0 at -0.0, so the zero is passed through here
+SRHIP_HD float m_log1p(float x) { return x == 0.0f ? x : (float)log1p((double)x); }
+SRHIP_HD double m_log1p(double x) { return x == 0.0 ? x : log1p(x); }
+SRHIP_HD float m_expm1(float x) { return x == 0.0f ? x : (float)expm1((double)x); }
+SRHIP_HD double m_expm1(double x) { return x == 0.0 ? x : expm1(x); }
 // exact in any IEEE implementation: no widening needed
 SRHIP_HD float m_sqrt(float x) { return sqrtf(x); }
 SRHIP_HD double m_sqrt(double x) { return sqrt(x); }

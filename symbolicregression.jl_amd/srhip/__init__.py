@@ -32,7 +32,8 @@ from .api import (
     update_baseline_loss,
 )
 from .dataset import Dataset
-from .device import Coalescer, Context, DeviceDataset, Program, device_count, get_context
+from .device import (Coalescer, Context, DeviceDataset, Program, device_count, get_context, isa_handler_count,
+                     isa_handler_name, isa_handler_ok)
 from .losses import (
     DWDMarginLoss,
     ExpLoss,

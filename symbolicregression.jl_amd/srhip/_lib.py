@@ -136,6 +136,10 @@ SIGNATURES = {
     "srhip_program_stats": (ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                            ctypes.POINTER(_i32)]),
     "srhip_program_derived": (ctypes.c_int, [_vp, ctypes.POINTER(_i32), _vp, _i32]),
+    "srhip_isa_handler_count": (_i32, []),
+    "srhip_isa_handler_name": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_char_p, _i32]),
+    "srhip_isa_handler_ok": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int]),
+    "srhip_program_handlers": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, ctypes.POINTER(_i32)]),
     "srhip_code_cache_stats": (ctypes.c_int, [ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "srhip_tail_share_parts": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp]),
 }

@@ -68,6 +68,26 @@ def get_context(device: int = 0) -> Context:
     return ctx
 
 
+def isa_handler_count() -> int:
+    """Handler ids of the interpreter's instruction set: 0 .. count - 1 (srhip_isa_handler_count)."""
+    return int(_lib.load().srhip_isa_handler_count())
+
+
+def isa_handler_name(h: int) -> str:
+    """srhip_isa_handler_name: "END", "PUSHLC2", "SUB.SA3", "POW.AS0", "UN.erfc", ..."""
+    buf = ctypes.create_string_buffer(32)
+    check(_lib.load().srhip_isa_handler_name(int(h), buf, 32))
+    return buf.value.decode()
+
+
+def isa_handler_ok(h: int, dtype) -> bool:
+    """Do the kernels of element type dtype implement handler h (srhip_isa_handler_ok)."""
+    rc = int(_lib.load().srhip_isa_handler_ok(int(h), _lib.dtype_code(dtype)))
+    if rc < 0:
+        raise ValueError(f"handler id {h} out of range")
+    return rc == 1
+
+
 def device_count() -> int:
     try:
         return int(_lib.load().srhip_device_count())
@@ -170,6 +190,16 @@ class Program:
         spec = np.zeros(64, dtype=np.uint32)
         check(_lib.load().srhip_program_derived(self.handle, ctypes.byref(n), ptr(spec), 64))
         return [(int(s) >> 16, int(s) & 0xffff) for s in spec[:n.value]]
+
+    def handlers(self, tree: int, derived: bool = True) -> np.ndarray:
+        """srhip_program_handlers: the handler ids of tree `tree`'s evaluation program in execution order
+        (END included); derived=False: the plain program of a program with derived columns."""
+        n = ctypes.c_int32()
+        lib = _lib.load()
+        check(lib.srhip_program_handlers(self.handle, int(tree), int(derived), None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        check(lib.srhip_program_handlers(self.handle, int(tree), int(derived), ptr(out), n.value, ctypes.byref(n)))
+        return out
 
     def eval_loss(self, ds: DeviceDataset, loss, idx=None):
         out = np.empty(self.ntrees, dtype=np.float64)

@@ -74,6 +74,48 @@ def test_version_and_errors_without_device():
             L.check(rc)
 
 
+def test_isa_handler_calls_without_device():
+    """srhip_isa_handler_count / _name / _ok and srhip_program_handlers (no device): bounds, names, the
+    Int32 subset, and a program's handlers with and without derived columns."""
+    import srhip as sr
+    import srhip._lib as L
+
+    lib = L.load()
+    n = lib.srhip_isa_handler_count()
+    assert n == 1 + 2 + 5 * 8 + 10 * 23 + 3 * 16 + 33
+    buf = ctypes.create_string_buffer(32)
+    assert lib.srhip_isa_handler_name(n, buf, 32) == L.ERR_INVALID
+    assert lib.srhip_isa_handler_name(0, None, 32) == L.ERR_INVALID
+    assert lib.srhip_isa_handler_name(n - 1, buf, 32) == 0 and buf.value == b"UN.cbrt"
+    assert lib.srhip_isa_handler_name(n - 1, buf, 4) == 0 and buf.value == b"UN."  # truncated, terminated
+    assert lib.srhip_isa_handler_ok(n, L.F32) < 0 and lib.srhip_isa_handler_ok(0, 7) < 0
+    names = [sr.isa_handler_name(h) for h in range(n)]
+    for dt in (np.float32, np.float64):
+        assert all(sr.isa_handler_ok(h, dt) for h in range(n))
+    int_ops = {nm.split(".")[0] for h, nm in enumerate(names) if "." in nm and sr.isa_handler_ok(h, np.int32)}
+    assert int_ops == {"ADD", "SUB", "MUL", "GREATER", "COND", "LOGICAL_OR", "LOGICAL_AND", "MAX", "MIN", "UN"}
+    assert {nm for h, nm in enumerate(names) if nm.startswith("UN.") and sr.isa_handler_ok(h, np.int32)} == {
+        "UN.neg", "UN.square", "UN.cube", "UN.abs", "UN.relu", "UN.sign"}
+    opts = sr.Options(binary_operators=("+", "*"), unary_operators=("cos", "exp"))
+    x1, x2 = (lambda: sr.Node(feature=1)), (lambda: sr.Node(feature=2))
+    trees = [sr.Node("+", sr.Node("cos", x1()), sr.Node("*", x2(), sr.Node(val=2.0))),
+             sr.Node("exp", sr.Node("cos", x1())), sr.Node("+", sr.Node(val=1.0), sr.Node(val=2.0))]
+    nodes, offs = sr.flatten(trees, opts, np.float32)
+    prog = sr.Program(None, nodes, offs, opts, np.float32)
+    assert prog.derived_columns() == [(names.index("UN.cos") - names.index("UN.neg"), 0)]
+    assert [names[h] for h in prog.handlers(0, derived=False)] == ["LOADF", "UN.cos", "PUSH0", "MUL.FC", "ADD.SA0", "END"]
+    assert [names[h] for h in prog.handlers(0)] == ["MUL.FC", "ADD.FA", "END"]
+    assert [names[h] for h in prog.handlers(1)] == ["LOADF", "UN.exp", "END"]
+    assert [names[h] for h in prog.handlers(2)] == ["LOADC", "END"]
+    cnt = ctypes.c_int32()
+    assert lib.srhip_program_handlers(prog.handle, 3, 1, None, 0, ctypes.byref(cnt)) == L.ERR_INVALID
+    assert lib.srhip_program_handlers(prog.handle, -1, 1, None, 0, ctypes.byref(cnt)) == L.ERR_INVALID
+    assert lib.srhip_program_handlers(prog.handle, 0, 1, None, 0, None) == L.ERR_INVALID
+    out = np.full(2, 999, np.uint32)
+    assert lib.srhip_program_handlers(prog.handle, 0, 0, L.ptr(out), 1, ctypes.byref(cnt)) == 0
+    assert cnt.value == 6 and out[0] == names.index("LOADF") and out[1] == 999  # never past cap
+
+
 def test_product_does_not_reference_oracle():
     """The shipped path never links or imports the oracle."""
     pkg = os.path.join(ROOT, "symbolicregression.jl_amd")
