@@ -438,6 +438,36 @@ int srhip_code_cache_stats(int64_t* hits, int64_t* misses, int64_t* inserts);
  * up to two parts as (block, first unit, end unit) triples to out[6] and returns their number (0: an
  * empty share), or a negative value for arguments out of range.  No device is needed. */
 int srhip_tail_share_parts(int32_t blocks, int32_t units, int32_t nshares, int32_t share, int32_t* out);
+/* How an evaluation would run (the launch plan), for tests: the decision eval launches
+ * and the order pre-planned at srhip_program_create both take, from shapes, device limits and the
+ * SRHIP_* switches of the calling process.  No device is needed.  kind: 0 small-population, 1
+ * persistent, 2 grid launch; mode: 0 loss, 1 prediction, 2 precise pass.  Returns 0, or a negative
+ * value for arguments out of range (null pointers, nlive < 0, m <= 0, num_cu <= 0, lds_max <= 0, an
+ * unknown dtype or mode). */
+typedef struct srhip_plan_query {
+  int32_t dtype, mode;    /* SRHIP_F32 / F64 / I32 */
+  int32_t nlive;          /* trees not failed statically */
+  int32_t maxfeat, nd;    /* staged feature columns, derived columns */
+  int32_t kmax, dkmax;    /* stack depth of the plain / derived-column program */
+  int32_t wide_ops;       /* asin, acos or atanh_clip among the unary operators */
+  int32_t weighted, sharded, have_recs;
+  int32_t loss_kind;
+  int32_t num_cu;
+  int32_t pad;
+  int64_t m;              /* rows */
+  int64_t lds_max;        /* the device's LDS bytes per workgroup */
+} srhip_plan_query;
+typedef struct srhip_plan_info {
+  int32_t kind, R, K, use_d;
+  int32_t rb_rows, nrb, groups, tpg, xlds;
+  int32_t nch, cpb, wg_waves;
+  int32_t probe_blocks, probe_tile_claims, wgs;
+  int32_t tail_slices, tail_blocks, tail_shares, expect_items;
+  int32_t fused, hot;
+  int32_t pad;
+  int64_t lds;            /* LDS bytes of a workgroup */
+} srhip_plan_info;
+int srhip_plan_eval(const srhip_plan_query* q, srhip_plan_info* out);
 
 /* ---- Cross-population request coalescer (8(b) "Threading") ----------------
  * The reference scores one tree per mutation from every population task concurrently

@@ -45,8 +45,6 @@
 
 using namespace srhip;
 
-static bool env_flag(const char* name);
-
 // ---------------------------------------------------------------------------------------------
 // errors
 // ---------------------------------------------------------------------------------------------
@@ -1593,10 +1591,6 @@ int srhip::upload_program(srhip_program& P, bool sync, bool defer, hipStream_t s
 // ---------------------------------------------------------------------------------------------
 // evaluation driver
 // ---------------------------------------------------------------------------------------------
-namespace {
-
-}  // namespace
-
 int srhip::make_view(srhip_ctx* ctx, const srhip_dataset* ds, const int64_t* idx, int64_t nidx, bool need_y, View& v) {
   if (need_y && !ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
   if (!idx) {
@@ -1628,11 +1622,6 @@ int srhip::make_view(srhip_ctx* ctx, const srhip_dataset* ds, const int64_t* idx
   if (ds->dtype != SRHIP_I32 && ds->nfeat > 0)
     HIP_TRY(hipMemcpyAsync(ctx->h_stats.p, ctx->vstats.p, (size_t)ds->nfeat * sizeof(FeatStat), hipMemcpyDeviceToHost,
                            ctx->stream));
-  double sw = 0.0;
-  if (ds->weighted) {
-    // sum of gathered weights, from the host copy kept at upload
-    // (computed below by the caller from the device buffer would need a sync; weights are small)
-  }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   v.X = ctx->vX.p;
   v.y = ds->has_y ? ctx->vy.p : nullptr;
@@ -1640,123 +1629,11 @@ int srhip::make_view(srhip_ctx* ctx, const srhip_dataset* ds, const int64_t* idx
   v.ld = ld;
   v.m = nidx;
   v.stats = (const FeatStat*)ctx->h_stats.p;
-  v.sum_w = sw;
+  v.sum_w = 0.0;  // (gathered_weight_sum fills it for the callers that need it)
   return SRHIP_OK;
 }
 
-LaunchPlan srhip::plan_launch(const srhip_ctx* ctx, int dtype, int64_t nxcols, bool weighted, bool with_y, int64_t m,
-                              int32_t ntrees, int tile, size_t budget, int waves) {
-  LaunchPlan L;
-  ntrees = std::max<int32_t>(1, ntrees);  // every tree may have failed statically
-  m = std::max<int64_t>(1, m);
-  const size_t es = dtype_size(dtype);
-  const int ncols = (int)nxcols + (with_y ? 1 : 0) + (weighted ? 1 : 0);
-  const int lo = std::max(tile, loss_chunk(dtype));  // row blocks are whole tiles and loss chunks
-  int rb = ROW_ALIGN;
-  while (rb > lo && (size_t)ncols * rb * es > budget) rb /= 2;
-  // do not make blocks much larger than the data
-  while (rb > lo && rb / 2 >= m) rb /= 2;
-  // diagnostic override (tuning runs): SRHIP_RB_ROWS = rows per workgroup, a power of two >= tile
-  static const int rb_env = [] { const char* e = getenv("SRHIP_RB_ROWS"); return e ? atoi(e) : 0; }();
-  if (rb_env >= lo && rb_env <= ROW_ALIGN && (rb_env & (rb_env - 1)) == 0 && rb_env < rb) rb = rb_env;
-  L.rb_rows = rb;
-  L.xlds = (size_t)ncols * rb * es <= budget;
-  L.lds = (L.xlds ? (size_t)ncols * rb * es : 0) + 16;
-  L.nrb = (int)((m + rb - 1) / rb);
-  const int target_blocks = 4 * ctx->num_cu;
-  int g = (target_blocks + L.nrb - 1) / L.nrb;
-  const int max_g = std::max(1, ntrees / (2 * waves));
-  g = std::max(1, std::min(g, max_g));
-  L.groups = g;
-  L.tpg = (ntrees + g - 1) / g;
-  L.groups = (ntrees + L.tpg - 1) / L.tpg;
-  return L;
-}
-
 namespace {
-
-// Tree groups of a launch (grid.y), as offsets into the order: the plan's uniform groups, or —
-// when the launch spans several waves of workgroups over the chip's 2-per-CU slots — the bulk in
-// g equal groups plus ~1/32 of the trees in halving tail groups (..., 32, 16, <=16).  Workgroups
-// dispatch group by group, so the small ones come last and fill the slots the bulk leaves idle:
-// identical workgroups over 977 row tiles x 2 groups use <= 95 % of 512 slots.  Measured on C2
-// (scripts/tail_sweep.sh): uniform 2.13 ms, tail 1/32 2.04-2.06 ms, 1/16 2.10, 1/8 2.18 (every
-// extra workgroup restages its rows and derived columns, so bigger tails or more bulk groups lose).
-// SRHIP_NO_TAIL=1: uniform groups.
-std::vector<int32_t> shape_groups(const LaunchPlan& L, int32_t ntrees, int num_cu) {
-  static const bool no_tail = [] { const char* e = getenv("SRHIP_NO_TAIL"); return e && *e && *e != '0'; }();
-  std::vector<int32_t> off(1, 0);
-  const bool tail = !no_tail && ntrees >= 128 && (int64_t)L.groups * L.nrb > 2 * (int64_t)num_cu;
-  if (!tail) {
-    for (int g = 0; g < L.groups; ++g) off.push_back(std::min(ntrees, off.back() + L.tpg));
-    return off;
-  }
-  // tuning hooks: SRHIP_TAIL_DIV (tail = trees / DIV, default 32), SRHIP_BULK_GROUPS (default: the
-  // plan's), SRHIP_TAIL_MIN (smallest tail group, default 16)
-  static const int tail_div = [] { const char* e = getenv("SRHIP_TAIL_DIV"); return e && atoi(e) >= 2 ? atoi(e) : 32; }();
-  static const int bulk_g = [] { const char* e = getenv("SRHIP_BULK_GROUPS"); return e ? atoi(e) : 0; }();
-  const int32_t tl = std::max<int32_t>(16, ntrees / tail_div), bulk = ntrees - tl;
-  const int groups = bulk_g > 0 ? std::min<int>(bulk_g, std::max(1, bulk / 16)) : L.groups;
-  const int32_t tpg = (bulk + groups - 1) / groups;
-  while (off.back() < bulk) off.push_back(std::min(bulk, off.back() + tpg));
-  static const int tail_min = [] { const char* e = getenv("SRHIP_TAIL_MIN"); return e && atoi(e) > 0 ? atoi(e) : 16; }();
-  int32_t t = tl;
-  while (t > tail_min) {
-    const int32_t h = t / 2;
-    off.push_back(off.back() + h);
-    t -= h;
-  }
-  if (t > 0) off.push_back(off.back() + t);
-  return off;
-}
-
-// trees sorted by estimated cost (desc), dealt to the groups in proportion to their sizes (each
-// tree to the group with the largest free fraction), so every group gets the same cost mix;
-// returns order [ntrees], group g's trees at [goff[g], goff[g+1])
-std::vector<int32_t> make_order(const srhip_program& P, const std::vector<int32_t>& trees,
-                                const std::vector<int32_t>& goff, bool derived) {
-  std::vector<int32_t> s(trees);
-  auto cost = [&](int32_t t) { return derived ? P.dcost[t] : P.info[t].cost; };
-  std::stable_sort(s.begin(), s.end(), [&](int32_t a, int32_t b) { return cost(a) > cost(b); });
-  const int groups = (int)goff.size() - 1;
-  std::vector<int32_t> order(s.size());
-  std::vector<int> fill(groups, 0);
-  for (int32_t t : s) {
-    int best = -1;
-    double bf = -1.0;
-    for (int g = 0; g < groups; ++g) {
-      const int cap = goff[g + 1] - goff[g];
-      if (fill[g] >= cap) continue;
-      const double f = (double)(cap - fill[g]) / cap;
-      if (f > bf) {
-        bf = f;
-        best = g;
-      }
-    }
-    order[(size_t)goff[best] + fill[best]++] = t;
-  }
-  return order;
-}
-
-// The hot form's slot records (SlotRec: what a wave reads per tree, in one scalar load) behind an
-// order and its group offsets: [order | goff | pad to 16 bytes | records], one upload.  The records
-// belong to the plan the order was made for: pc0 and the mask are the derived-column program's when
-// that plan evaluates it.  Returns the records' offset in int32 units.
-static int append_slot_records(const srhip_program& P, std::vector<int32_t>& order, int nl, bool derived) {
-  while (order.size() % 4 != 0) order.push_back(0);
-  const int at = (int)order.size();
-  order.resize((size_t)at + 4 * (size_t)nl);
-  for (int sl = 0; sl < nl; ++sl) {
-    const int32_t t = order[sl];
-    const uint64_t m = derived ? P.dmask[t] : 0;
-    int32_t* r = order.data() + at + 4 * (size_t)sl;
-    r[0] = t;
-    r[1] = derived ? P.dprog_off[t] : P.prog_off[t];
-    r[2] = (int32_t)(uint32_t)m;
-    r[3] = (int32_t)(uint32_t)(m >> 32);
-  }
-  return at;
-}
 
 // ---- the did_succeed decision, from (possibly all-reduced) partials ----------------------------
 // Partials layout (the C ABI's srhip_eval_loss_partials): sums[2t] = sum of (w *) l over the rows,
@@ -1943,11 +1820,6 @@ int srhip::check_eval_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_
   return SRHIP_OK;
 }
 
-static bool env_flag(const char* name) {
-  const char* e = env_get(name);
-  return e && *e && *e != '0';
-}
-
 // run_eval's device-decided precise pass: the reduction lists the trees whose overflow bound needs
 // the precise pass, and the precise launch + its reduction follow on the stream before the one host
 // synchronisation (no host round trip between the main launch and the precise pass)
@@ -2018,7 +1890,7 @@ static int enqueue_dev_precise(srhip_ctx* ctx, const srhip_dataset* ds, const sr
   const int stride = std::max(1, P->max_ops);
   const int Rp = pick_rows_per_lane(dtype, K_MAX, MODE_PRECISE, v.m);
   G = std::max(1, std::min(G, cap));
-  LaunchPlan Lp = plan_launch(ctx, dtype, ds->nfeat, false, false, v.m, G, 64 * Rp);
+  LaunchPlan Lp = plan_launch(ctx->num_cu, dtype, ds->nfeat, false, false, v.m, G, 64 * Rp);
   Lp.rb_rows = 64 * Rp;
   Lp.nrb = (int)((v.m + Lp.rb_rows - 1) / Lp.rb_rows);
   {
@@ -2065,14 +1937,13 @@ static int enqueue_dev_precise(srhip_ctx* ctx, const srhip_dataset* ds, const sr
 // stream at once (srhip_eval_loss_submit), each with its own result set.
 struct EvalJob {
   ResultSet* rs = nullptr;
-  bool launched = false, persistent = false, devp = false;
+  bool launched = false, devp = false;
   int mode = 0, dtype = 0;
   int32_t nt = 0;
-  int32_t expect_items = 0;  // persistent launches: the items its workgroups must report evaluated
+  EvalPlan pl{};  // the launch's plan (persistent, fused, expect_items)
   std::vector<int32_t> live;
   UndecidedList ul;
   DevBuf pred;  // MODE_PRED's device output (synchronous calls only)
-  bool fused = false;  // single-block launch: the interpreter wrote the records (no reduction)
   float fbound = 0.0f;  // Float32: the features' max |x| (the +/- bound's F)
 };
 // the features' max |x| over a view's rows (+Inf if any entry is non-finite), rounded up to Float32:
@@ -2086,6 +1957,16 @@ static float feature_bound(const View& v, int64_t nfeat) {
   if (!v.stats && nfeat > 0) return INFINITY;
   const float r = (float)F;
   return (double)r >= F ? r : std::nextafter(r, INFINITY);
+}
+
+// What plan_eval reads of a context and a program with nlive live trees (in EvalPlanIn's order): an
+// unweighted, unsharded MODE_LOSS launch of loss kind 0 over WIDE_MIN_ROWS rows -- the launch
+// plan_persistent_order assumes -- until the caller says otherwise.  A persistent launch's order always
+// carries its slot records (eval_issue makes them).
+static EvalPlanIn plan_input(const srhip_ctx* ctx, const srhip_program& P, int32_t nlive) {
+  return EvalPlanIn{P.dtype, MODE_LOSS, nlive, WIDE_MIN_ROWS, P.maxfeat, (int32_t)P.dspec.size(), P.kmax, P.dkmax,
+                    has_wide_ops(P.unaops), /*weighted*/ false, /*sharded*/ false, /*have_recs*/ true,
+                    /*loss_kind*/ 0, ctx->num_cu, ctx->lds_max};
 }
 
 static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode, const srhip_loss* loss,
@@ -2116,112 +1997,18 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
     if (!(P->dec.size() == (size_t)nt ? P->dec[t].static_fail : P->info[t].static_fail)) live.push_back(t);
   if (live.empty()) return SRHIP_OK;
   const size_t es = dtype_size(dtype);
-  // stack slots of the kernel variant; the wide operators live only in the K_MAX variant
-  bool wide = false;
-  for (int32_t u : P->unaops) wide |= u == SRHIP_OP_ASIN || u == SRHIP_OP_ACOS || u == SRHIP_OP_ATANH_CLIP;
-  auto kvariant = [&](int32_t kmax) { return wide ? K_MAX : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : 8)); };
-  // derived-column program when its staging fits LDS (the R = 16 variant runs 2 workgroups per CU,
-  // so it may use 80 KB); otherwise the plain program
-  const int nd = (int)P->dspec.size();
-  bool use_d = false;
-  int K = 0, R = 0;
-  LaunchPlan L{};
-  // LDS a workgroup may stage: the 16-wave variant runs one workgroup per CU (160 KB, less the
-  // kernel's static arrays); 8-wave workgroups run two (derived-column programs) or more
-  // (the device's LDS per workgroup, read once per context, less 8 KB for the kernel's static arrays)
-  const size_t lds_dev = (size_t)ctx->lds_max;
-  auto lds_budget = [lds_dev](int r, int k, bool derived) -> size_t {
-    if (eval_waves(r, k) >= 16) return lds_dev - 8 * 1024;
-    return std::min<size_t>(lds_dev / 2, derived ? 64 * 1024 - 512 : 64 * 1024 - 64);
-  };
-  // Persistent launch (the wide Float32 variant's loss launches): one workgroup per CU claims short
-  // row blocks from a counter and interprets the WHOLE population over each -- the dataset is read
-  // from HBM once, every derived column is computed once per row block for all trees, and the tail
-  // is one short block instead of a wave of workgroups.  A probe launch first evaluates the leading
-  // row blocks with many small tree groups, so trees that fail there (DynamicExpressions' early
-  // return: did_succeed = false whatever the other rows hold) are skipped by every later block.
-  // SRHIP_NO_PERSISTENT=1: the grid launch; SRHIP_PRB_ROWS: row-block rows (default 2048: C2, one
-  // MI355X, same box: 1024 rows 1.31 ms, 2048 1.19, 4096 1.35, grid launch 1.33);
-  // SRHIP_PROBE_BLOCKS: probe row blocks (default 4).
-  // (read per launch: tests and the bench toggle them inside one process)
-  const bool no_persistent = env_flag("SRHIP_NO_PERSISTENT");
-  const int prb_env = env_int("SRHIP_PRB_ROWS", 0);
-  const int probe_env = env_int("SRHIP_PROBE_BLOCKS", -1);
-  bool persistent = false;
-  int probe_blocks = 0;
-  // Few trees over many rows (the search's coalesced launches: C3 carries ~2.4 trees per launch over
-  // 10M rows): a workgroup of one wave per tree per loss chunk of rows, X read from global memory.
-  // The staged launches give each tree one wave per CU -- a 2048-row block staged for 2 trees leaves
-  // 14 of its 16 waves idle.  SRHIP_SMALL_POP: the largest population launched this way (0: never).
-  const int small_max = env_int("SRHIP_SMALL_POP", 16);
-  const bool small = (mode == MODE_LOSS || mode == MODE_PRED) && debug_stop() == 0 && (int)live.size() <= small_max &&
-                     v.m >= (int64_t)64 * ROW_ALIGN;
-  if (small) {
-    K = kvariant(P->kmax);
-    R = pick_rows_per_lane(dtype, K, mode, v.m);
-    L.rb_rows = std::max(64 * R, loss_chunk(dtype));
-    L.xlds = false;
-    L.lds = 16;
-    L.nrb = (int)((v.m + L.rb_rows - 1) / L.rb_rows);
-    L.groups = 1;
-    L.tpg = (int)live.size();
-  }
-  if (!small) {
-    const int Kp = kvariant(P->kmax);
-    persistent = !no_persistent && mode == MODE_LOSS && debug_stop() == 0 && dtype == SRHIP_F32 &&
-                 pick_rows_per_lane(dtype, Kp, mode, v.m) == R_F32_WIDE && R_F32_WIDE != R_F32 &&
-                 (nd == 0 || kvariant(P->dkmax) == Kp);
-    if (persistent) {
-      K = Kp;
-      R = R_F32_WIDE;
-      const int tile = 64 * R;
-      int rb = prb_env >= tile && prb_env <= ROW_ALIGN && (prb_env & (prb_env - 1)) == 0 ? prb_env : 2048;
-      rb = std::max(rb, std::max(tile, loss_chunk(dtype)));
-      const size_t es = dtype_size(dtype);
-      const int base_cols = P->maxfeat + 1 + (weighted ? 1 : 0);
-      use_d = nd > 0 && (size_t)(base_cols + nd) * rb * es <= lds_budget(R, K, true);
-      const int ncols = base_cols + (use_d ? nd : 0);
-      if ((size_t)ncols * rb * es > lds_budget(R, K, false)) {
-        persistent = false;  // the block does not fit LDS: grid launch over global reads
-        use_d = false;
-      } else {
-        L.rb_rows = rb;
-        L.xlds = true;
-        L.lds = (size_t)ncols * rb * es + 16;
-        L.nrb = (int)((v.m + rb - 1) / rb);
-        L.groups = 1;
-        L.tpg = (int)live.size();
-        probe_blocks = probe_env >= 0 ? probe_env : 4;
-        probe_blocks = L.nrb >= 16 * std::max(1, probe_blocks) ? probe_blocks : 0;
-      }
-    }
-  }
-  if (!small && !persistent && nd > 0 && mode != MODE_PRECISE) {
-    K = kvariant(P->dkmax);
-    R = pick_rows_per_lane(dtype, K, mode, v.m);
-    L = plan_launch(ctx, dtype, P->maxfeat + nd, weighted, mode == MODE_LOSS, v.m, (int32_t)live.size(), 64 * R,
-                    lds_budget(R, K, true), eval_waves(R, K));
-    use_d = L.xlds;
-    // ... and only when its columns do not shrink the row block: a wave's early exit of a failed tree
-    // saves the rest of its row block, and shorter blocks lose more than the shared columns save
-    // (C2, one MI355X, warm, separate processes: 10 columns at 2048-row blocks 1.29 ms vs the plain
-    // program at 4096 rows 1.27 ms with 16-wave workgroups; 1.56 vs 1.41 ms at 1024 / 2048 rows with
-    // 8-wave workgroups)
-    const char* always = env_get("SRHIP_DERIVE_ALWAYS");  // (tests: the derived program whatever the blocks)
-    if (use_d && !(always && *always && *always != '0')) {
-      const int Kp = kvariant(P->kmax), Rp = pick_rows_per_lane(dtype, Kp, mode, v.m);
-      const LaunchPlan Lp = plan_launch(ctx, dtype, P->maxfeat, weighted, mode == MODE_LOSS, v.m, (int32_t)live.size(),
-                                        64 * Rp, lds_budget(Rp, Kp, false), eval_waves(Rp, Kp));
-      if (Lp.xlds && Lp.rb_rows > L.rb_rows) use_d = false;
-    }
-  }
-  if (!small && !persistent && !use_d) {
-    K = kvariant(P->kmax);
-    R = pick_rows_per_lane(dtype, K, mode, v.m);
-    L = plan_launch(ctx, dtype, P->maxfeat, weighted, mode == MODE_LOSS, v.m, (int32_t)live.size(), 64 * R,
-                    lds_budget(R, K, false), eval_waves(R, K));
-  }
   const int nl = (int)live.size();
+  // how the launch runs (srhip_plan.h): from here on the plan is only read
+  EvalPlanIn in = plan_input(ctx, *P, nl);
+  in.mode = mode;
+  in.m = v.m;
+  in.weighted = weighted;
+  in.sharded = sd != nullptr;
+  in.loss_kind = loss ? loss->kind : 0;
+  const EvalPlan& pl = J.pl = plan_eval(in);
+  const LaunchPlan& L = pl.L;
+  const bool persistent = pl.kind == PLAN_PERSISTENT, use_d = pl.use_d;
+  const int R = pl.R, K = pl.K, nch = pl.nch, cpb = pl.cpb, probe_blocks = pl.probe_blocks;
   const void* d_order;
   int rec_at = -1;  // the plan's slot records behind the order (int32 units), if it has them
   // persistent launches: one group, the order globally by descending cost (the probe's uniform
@@ -2258,8 +2045,6 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
     d_order = P->ord_dev;
     rec_at = P->ord_recs;
   }
-  const int nch = (int)((v.m + loss_chunk(dtype) - 1) / loss_chunk(dtype));
-  const int cpb = L.rb_rows / loss_chunk(dtype);  // loss chunks per row block (row blocks are whole chunks)
   HIP_TRY(ctx->slab_loss.ensure((size_t)nl * L.nrb * cpb * 8));
   HIP_TRY(ctx->slab_chk.ensure((size_t)nl * L.nrb * 8));
   // the reduction writes the per-tree results straight into coherent pinned host memory (no
@@ -2271,7 +2056,7 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
   a.code = use_d ? P->dcode_dev : P->code_dev;
   a.prog_off = use_d ? P->doff_dev : P->off_dev;
   a.order = (const int32_t*)d_order;
-  a.nd = use_d ? nd : 0;
+  a.nd = use_d ? in.nd : 0;
   a.dspec = use_d ? P->dspec_dev : nullptr;
   a.dmask = use_d ? P->dmask_dev : nullptr;
   if (dtype == SRHIP_F32) {
@@ -2301,11 +2086,8 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
   a.has_y = mode == MODE_LOSS ? 1 : 0;
   a.max_steps = use_d ? P->dmax_len : P->max_len;
   a.debug_stop = debug_stop();
-  if (small) a.wg_waves = (int)live.size();  // one wave per tree (at most the variant's waves)
-  // one row block: the waves finish the per-tree reduction themselves (SRHIP_NO_FUSED_REDUCE=1: the
-  // reduce kernel instead; read per launch)
-  const char* nofuse = env_get("SRHIP_NO_FUSED_REDUCE");
-  if (L.nrb == 1 && !sd && !(nofuse && *nofuse && *nofuse != '0')) {
+  a.wg_waves = pl.wg_waves;
+  if (pl.fused) {  // one row block: the waves finish the per-tree reduction themselves
     a.fused = 1;
     a.fused_loss = mode == MODE_LOSS ? rs->h_loss.p : nullptr;
     a.fused_chk = dtype == SRHIP_I32 ? nullptr : rs->h_chk.p;
@@ -2340,8 +2122,7 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
   dim3 grid(L.nrb, (unsigned)goff.size() - 1);
   // a probe with tile claims zeroes the counter itself, so a launch still in flight (an earlier
   // submitted evaluation, not yet seen to drain) needs no fill in front of this one
-  const bool probe_zeroes = probe_blocks > 0 && !env_flag("SRHIP_PROBE_TREE_CLAIMS");
-  if (persistent && (!ctx->block_ctr.p || (ctx->block_ctr_dirty && !probe_zeroes))) {
+  if (persistent && (!ctx->block_ctr.p || (ctx->block_ctr_dirty && !pl.probe_tile_claims))) {
     // zeroed once: every persistent launch that drains its claims leaves it at zero (its last claim
     // resets it); again after a launch that was never seen to complete (an error return between the
     // launch and its synchronisation, or a lost row block below)
@@ -2369,7 +2150,7 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
       // probe's duration is that tree's); chk / rows of the probe blocks combine by atomics from 0
       // (the probe's workgroups zero their own combining entries and the persistent launch's block
       // counter: no memset launches on the stream)
-      if (probe_zeroes) {
+      if (pl.probe_tile_claims) {
         q.tile_claims = 1;
         q.zero_ctr = (int32_t*)ctx->block_ctr.p;
       }
@@ -2394,58 +2175,17 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
       HIP_TRY(hipMemcpyAsync(ctx->block_ctr.p, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
       HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    const int nmain = L.nrb - probe_blocks;
-    // The last round in equal shares (srhip_tail_shares.h).  Whole blocks on wgs workgroups leave the
-    // Lb = nmain % wgs blocks past the last whole round to Lb workgroups while the others idle for a
-    // block: C2's 485 blocks on 256 workgroups last 2.0 block times for 1.894 of work, and 49 blocks
-    // (100k rows) run on 49 of 256 CUs.  Claiming those blocks as S population slices each, one by
-    // one, cannot help: the round then lasts ceil(Lb S / wgs) / S block times -- C2: 8/8 at S = 8,
-    // 15/16 at S = 16 -- and every slice restages its block and re-derives its columns (C2, same box:
-    // whole blocks 1.215 ms, S = 8 1.250, 16 1.278).  Instead the Lb S units are dealt to the
-    // workgroups as nshares contiguous ranges of near-equal length, one claim each: a share stages at
-    // most two blocks however many units it holds, and at S = 128 C2's round lasts 115/128 block times
-    // (units are an index mapping, not a staging: the finest S of the measured 32 / 64 / 128 is as fast
-    // or faster at 300k and 1M rows, profiles/r07_tail_shares.txt).
-    // A launch of fewer blocks than workgroups is all last round (nfull = 0) and fills the device.
-    //   SRHIP_TAIL_BALANCE=0: whole blocks; SRHIP_TAIL_SLICES=S > 1: units per block (default
-    //   TAIL_UNITS, at most 128); SRHIP_TAIL_SHARE_ROUNDS=2: 2 wgs shares; SRHIP_PERSISTENT_WGS=n
-    //   (tests): at most n workgroups.  Read per launch.
-    // Gate: the average share holds a tree per wave of a workgroup, nl Lb >= waves nshares -- below
-    // that a share's waves idle and its staging buys nothing; then whole blocks, as before.
-    constexpr int TAIL_UNITS = 128;
-    const int wgs_cap = std::max(1, std::min(env_int("SRHIP_PERSISTENT_WGS", ctx->num_cu), ctx->num_cu));
-    const int units_env = env_int("SRHIP_TAIL_SLICES", 0);
-    const int units = units_env > 1 ? std::min(units_env, 128) : TAIL_UNITS;
-    int wgs = std::max(1, std::min(nmain, wgs_cap));
-    a.tail_slices = 1;
-    a.tail_blocks = 0;
-    a.tail_shares = 0;
-    if (env_int("SRHIP_TAIL_BALANCE", 1) != 0 && nmain % wgs_cap != 0) {
-      const int lb = nmain % wgs_cap;
-      const int nshares = wgs_cap * (env_int("SRHIP_TAIL_SHARE_ROUNDS", 1) == 2 ? 2 : 1);
-      if ((int64_t)nl * lb >= (int64_t)eval_waves(R, K) * nshares &&
-          (int64_t)lb * units * nshares < ((int64_t)1 << 31)) {
-        wgs = wgs_cap;
-        a.tail_slices = units;
-        a.tail_blocks = lb;
-        a.tail_shares = nshares;
-      }
-    }
-    J.expect_items = nmain - a.tail_blocks + a.tail_shares;
-    // the hot form (FORM_HOT; launch_eval_f32w takes it when the launch carries records): this launch of
-    // the wide Float32 loss kernel, slab results, no diagnostics, every slab index in 32 bits.
-    // SRHIP_NO_HOT_FORM=1: the general form (read per launch)
-    if (R == R_F32_WIDE && K == 2 && rec_at >= 0 && !a.fused && a.slab_rows && !a.dbg && a.debug_stop == 0 &&
-        a.loss_kind >= 0 && a.loss_kind < 256 && (int64_t)nl * L.nrb * cpb < ((int64_t)1 << 31) && !env_flag("SRHIP_NO_HOT_FORM"))
-      a.recs = (const SlotRec*)((const int32_t*)d_order + rec_at);
-    HIP_TRY(launch_eval(dtype, a, R, K, mode, true, dim3(wgs, 1), L.lds, ctx->stream));
+    a.tail_slices = pl.tail_slices;  // the last round in equal shares (plan_eval)
+    a.tail_blocks = pl.tail_blocks;
+    a.tail_shares = pl.tail_shares;
+    if (pl.hot) a.recs = (const SlotRec*)((const int32_t*)d_order + rec_at);
+    HIP_TRY(launch_eval(dtype, a, R, K, mode, true, dim3(pl.wgs, 1), L.lds, ctx->stream));
     if (a.recs) ++ctx->hot_launches;  // (counted once the launch is enqueued)
   } else {
     HIP_TRY(launch_eval(dtype, a, R, K, mode, L.xlds, grid, L.lds, ctx->stream));
   }
   HIP_TRY(hipEventRecord(rs->ev1, ctx->stream));
   J.launched = true;
-  J.persistent = persistent;
   J.devp = devp;
   if (trace_on()) {  // poll the kernel's progress words for up to 10 s, then abort loudly
     const volatile int32_t* d = (const volatile int32_t*)ctx->h_dbg.p;
@@ -2486,7 +2226,6 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
     ul.rows = (double)v.m;
     ul_groups = std::min(ul.umax, std::max(4, P->und_hint + 2));
   }
-  J.fused = a.fused != 0;
   if (dtype == SRHIP_F32) {  // the reduction raises each tree's statistic to its +/- bound
     ul.sbound = P->sbound_dev;
     ul.fbound = J.fbound;
@@ -2520,7 +2259,7 @@ static int eval_collect(srhip_ctx* ctx, const srhip_program* P, const View& v, d
   const int dtype = J.dtype, mode = J.mode;
   const int32_t nt = J.nt;
   const std::vector<int32_t>& live = J.live;
-  const bool persistent = J.persistent, devp = J.devp;
+  const bool persistent = J.pl.kind == PLAN_PERSISTENT, devp = J.devp;
   const UndecidedList& ul = J.ul;
   ctx->last_ev0 = rs->ev0;
   ctx->last_ev1 = rs->ev1;
@@ -2550,7 +2289,7 @@ static int eval_collect(srhip_ctx* ctx, const srhip_program* P, const View& v, d
     if (dtype == SRHIP_F32) {
       const float m = ((const float*)r_chk.data())[t];
       // a single-block launch's records come straight from the interpreter: its +/- bound applied here
-      chk[t] = J.fused ? skip_bound_apply(m, P->sbound.data() + 4 * (size_t)t, J.fbound) : m;
+      chk[t] = J.pl.fused ? skip_bound_apply(m, P->sbound.data() + 4 * (size_t)t, J.fbound) : m;
     } else if (dtype == SRHIP_F64) {
       chk[t] = ((const double*)r_chk.data())[t];
     }
@@ -2560,9 +2299,9 @@ static int eval_collect(srhip_ctx* ctx, const srhip_program* P, const View& v, d
     // item count (a counter left non-zero by a launch that never drained would make this one skip
     // blocks silently -- and leave the skipped blocks' stale partials in the slabs)
     const int64_t done = ((const int64_t*)rs->h_rows.p)[nt];
-    if (done != J.expect_items)
+    if (done != J.pl.expect_items)
       return fail(SRHIP_ERR_DEVICE, "persistent launch evaluated %lld of %d row-block items (row-block counter "
-                  "not at zero); the counter is reset for the next launch", (long long)done, (int)J.expect_items);
+                  "not at zero); the counter is reset for the next launch", (long long)done, J.pl.expect_items);
     ctx->block_ctr_dirty = false;
   }
   // the launch's work, counted on the device (rows each tree was evaluated on)
@@ -2602,7 +2341,7 @@ static int eval_precise(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pro
   for (size_t i = 0; i < (size_t)nu * stride; ++i) opsums[i] = 0.0;
   if (nu == 0 || dtype == SRHIP_I32) return SRHIP_OK;
   const int R = pick_rows_per_lane(dtype, K_MAX, MODE_PRECISE, v.m);
-  LaunchPlan Lp = plan_launch(ctx, dtype, ds->nfeat, false, false, v.m, nu, 64 * R);
+  LaunchPlan Lp = plan_launch(ctx->num_cu, dtype, ds->nfeat, false, false, v.m, nu, 64 * R);
   Lp.groups = 1;
   Lp.tpg = nu;
   const size_t slab_bytes = (size_t)nu * stride * Lp.nrb * sizeof(double);
@@ -2950,37 +2689,23 @@ int srhip::run_eval_sharded(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
 // pageable-source copy the runtime stages synchronously) in front of the first launch.  Assumes an
 // unweighted dataset of >= WIDE_MIN_ROWS rows; any other launch re-plans as before (the key differs).
 static void plan_persistent_order(const srhip_ctx* ctx, srhip_program& P) {
-  if (!ctx || P.dtype != SRHIP_F32 || P.ntrees == 0) return;
-  if (env_flag("SRHIP_NO_PERSISTENT") || env_flag("SRHIP_NO_PREPLAN")) return;
-  bool wide = false;
-  for (int32_t u : P.unaops) wide |= u == SRHIP_OP_ASIN || u == SRHIP_OP_ACOS || u == SRHIP_OP_ATANH_CLIP;
-  auto kvariant = [&](int32_t kmax) { return wide ? K_MAX : (kmax <= 2 ? 2 : (kmax <= 4 ? 4 : 8)); };
-  const int nd = (int)P.dspec.size();
-  const int Kp = kvariant(P.kmax);
-  if (pick_rows_per_lane(SRHIP_F32, Kp, MODE_LOSS, WIDE_MIN_ROWS) != R_F32_WIDE || R_F32_WIDE == R_F32) return;
-  if (nd != 0 && kvariant(P.dkmax) != Kp) return;
-  const int prb_env = env_int("SRHIP_PRB_ROWS", 0);
-  const int tile = 64 * R_F32_WIDE;
-  int rb = prb_env >= tile && prb_env <= ROW_ALIGN && (prb_env & (prb_env - 1)) == 0 ? prb_env : 2048;
-  rb = std::max(rb, std::max(tile, loss_chunk(SRHIP_F32)));
-  const size_t budget = (size_t)ctx->lds_max - 8 * 1024;  // the 16-wave variant: one workgroup per CU
-  const int base_cols = P.maxfeat + 1;
-  const bool use_d = nd > 0 && (size_t)(base_cols + nd) * rb * 4 <= budget;
-  if ((size_t)(base_cols + (use_d ? nd : 0)) * rb * 4 > budget) return;
+  if (!ctx || P.ntrees == 0 || env_flag("SRHIP_NO_PREPLAN")) return;
   std::vector<int32_t> live;
   live.reserve(P.ntrees);
   for (int32_t t = 0; t < P.ntrees; ++t)
     if (!P.info[t].static_fail) live.push_back(t);
   if (live.empty()) return;
   const int nl = (int)live.size();
+  const EvalPlan pl = plan_eval(plan_input(ctx, P, nl));
+  if (pl.kind != PLAN_PERSISTENT) return;
   const std::vector<int32_t> goff{0, nl};
   std::lock_guard<std::mutex> g(P.ord_mu);
-  P.ord_host = make_order(P, live, goff, use_d);
+  P.ord_host = make_order(P, live, goff, pl.use_d);
   P.ord_host.insert(P.ord_host.end(), goff.begin(), goff.end());
-  P.ord_recs = append_slot_records(P, P.ord_host, nl, use_d);
-  P.ord_key[0] = 1;
-  P.ord_key[1] = nl;
-  P.ord_key[2] = (int)use_d;
+  P.ord_recs = append_slot_records(P, P.ord_host, nl, pl.use_d);
+  P.ord_key[0] = pl.L.groups;
+  P.ord_key[1] = pl.L.tpg;
+  P.ord_key[2] = (int)pl.use_d;
   P.ord_goff = goff;
 }
 

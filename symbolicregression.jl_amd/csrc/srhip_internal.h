@@ -1,5 +1,6 @@
 // srhip_internal.h — library-internal declarations shared by the translation units of libsrhip.so
-// (srhip_host.cpp: compiler, datasets, evaluation driver, C ABI; srhip_optim.cpp: constant
+// (srhip_host.cpp: compiler, datasets, evaluation driver, C ABI; srhip_plan.cpp: the launch decision
+// and the launch order, device-free; srhip_optim.cpp: constant
 // gradients and the batched BFGS constant optimizer).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,7 @@
 #include "../../include/srhip.h"
 #include "srhip_isa.h"
 #include "srhip_kernels.h"
+#include "srhip_plan.h"
 
 namespace srhip {
 
@@ -331,7 +333,7 @@ struct srhip_program {
 
 namespace srhip {
 
-// ---- evaluation views and launch planning (srhip_host.cpp) ----------------------------------
+// ---- evaluation views (srhip_host.cpp; launch planning: srhip_plan.h) -------------------------
 struct View {
   const void* X;
   const void* y;
@@ -343,11 +345,6 @@ struct View {
   // srhip_optim.cpp derived_view): the feature columns staged per row block; -1: the dataset's
   int32_t nfeat_x = -1;
   int32_t nd_x = 0;  // its derived columns (then as many tangent-zero columns)
-};
-struct LaunchPlan {
-  int rb_rows, nrb, groups, tpg;
-  bool xlds;
-  size_t lds;
 };
 int compile_program(srhip_program& P);       // eval program (+ invalidates the gradient program)
 extern thread_local double g_patch_scan_s, g_patch_copy_s;  // optimiser timing split (SRHIP_OPTIM_TIMING), per thread
@@ -365,9 +362,6 @@ bool spec_instantiate(srhip_program& P, int32_t slot, int32_t t, const double* c
 int upload_program(srhip_program& P, bool sync = true, bool defer = false, hipStream_t stream = nullptr);
 int make_view(srhip_ctx* ctx, const srhip_dataset* ds, const int64_t* idx, int64_t nidx, bool need_y, View& v);
 int gathered_weight_sum(srhip_ctx* ctx, const srhip_dataset* ds, int64_t nidx, View& v);
-// ncols: feature (+ derived) columns staged; lds_budget: bytes of LDS a workgroup may use
-LaunchPlan plan_launch(const srhip_ctx* ctx, int dtype, int64_t ncols, bool weighted, bool with_y, int64_t m,
-                       int32_t ntrees, int rows_per_tile, size_t lds_budget = 64 * 1024 - 64, int waves = EVAL_WAVES);
 // did_succeed decision of tree t from partials in the srhip_eval_loss_partials layout:
 // 0 ok, 1 fail, 2 undecided (only the sums' feature / row-count entries are read)
 int decide_tree(const TreeInfo& I, const srhip_program& P, int64_t nfeat, const double* sums, double chk);
@@ -415,6 +409,10 @@ int stream_wait(srhip_ctx* ctx);
 inline int env_int(const char* name, int dflt) {
   const char* e = env_get(name);
   return e && *e ? atoi(e) : dflt;
+}
+inline bool env_flag(const char* name) {
+  const char* e = env_get(name);
+  return e && *e && *e != '0';
 }
 inline double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();

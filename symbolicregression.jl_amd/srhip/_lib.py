@@ -61,6 +61,19 @@ class OptimOptions(ctypes.Structure):
                 ("g_tol", ctypes.c_double)]
 
 
+class PlanQuery(ctypes.Structure):  # struct srhip_plan_query
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "dtype", "mode", "nlive", "maxfeat", "nd", "kmax", "dkmax", "wide_ops", "weighted", "sharded", "have_recs",
+        "loss_kind", "num_cu", "pad")] + [("m", ctypes.c_int64), ("lds_max", ctypes.c_int64)]
+
+
+class PlanInfo(ctypes.Structure):  # struct srhip_plan_info
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "kind", "R", "K", "use_d", "rb_rows", "nrb", "groups", "tpg", "xlds", "nch", "cpb", "wg_waves",
+        "probe_blocks", "probe_tile_claims", "wgs", "tail_slices", "tail_blocks", "tail_shares", "expect_items",
+        "fused", "hot", "pad")] + [("lds", ctypes.c_int64)]
+
+
 class SrhipError(RuntimeError):
     """A nonzero status from libsrhip (message from srhip_last_error)."""
 
@@ -142,6 +155,7 @@ SIGNATURES = {
     "srhip_program_handlers": (ctypes.c_int, [_vp, _i32, _i32, _vp, _i32, ctypes.POINTER(_i32)]),
     "srhip_code_cache_stats": (ctypes.c_int, [ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "srhip_tail_share_parts": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp]),
+    "srhip_plan_eval": (ctypes.c_int, [ctypes.POINTER(PlanQuery), ctypes.POINTER(PlanInfo)]),
 }
 
 _lib = None

@@ -116,6 +116,23 @@ def test_isa_handler_calls_without_device():
     assert cnt.value == 6 and out[0] == names.index("LOADF") and out[1] == 999  # never past cap
 
 
+def test_plan_eval_without_device():
+    """srhip_plan_eval (no device): the struct layouts of the binding, a plan, and arguments out of range
+    (tests/test_eval_plan.py checks the plans themselves)."""
+    import srhip._lib as L
+
+    lib = L.load()
+    assert ctypes.sizeof(L.PlanQuery) == 14 * 4 + 2 * 8 and L.PlanQuery.m.offset == 56
+    assert ctypes.sizeof(L.PlanInfo) == 22 * 4 + 8 and L.PlanInfo.lds.offset == 88
+    q = L.PlanQuery(dtype=L.F32, mode=0, nlive=64, m=4096, maxfeat=5, kmax=2, have_recs=1, num_cu=256, lds_max=163840)
+    out = L.PlanInfo()
+    assert lib.srhip_plan_eval(ctypes.byref(q), ctypes.byref(out)) == 0
+    assert (out.kind, out.R, out.K, out.rb_rows, out.nrb, out.lds) == (1, 16, 2, 2048, 2, 6 * 2048 * 4 + 16)
+    assert lib.srhip_plan_eval(None, ctypes.byref(out)) < 0 and lib.srhip_plan_eval(ctypes.byref(q), None) < 0
+    q.m = 0
+    assert lib.srhip_plan_eval(ctypes.byref(q), ctypes.byref(out)) < 0
+
+
 def test_product_does_not_reference_oracle():
     """The shipped path never links or imports the oracle."""
     pkg = os.path.join(ROOT, "symbolicregression.jl_amd")

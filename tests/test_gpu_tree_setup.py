@@ -170,3 +170,47 @@ def test_records_belong_to_program_and_plan(ctx, oracle, monkeypatch):
     assert np.array_equal(ok3, oka) and np.array_equal(_bits(l3), _bits(la))
     pa.close()
     pb.close()
+
+
+def test_reported_plan_is_the_launch_taken(ctx, monkeypatch):
+    """32 trees x 3 features x 8,192 rows (four row blocks: no probe, whole blocks): srhip_plan_eval says
+    persistent and hot, and the hot-form counter rises by exactly one over one eval_loss; with
+    SRHIP_NO_HOT_FORM=1 it says not hot, the counter stays, and losses and ok flags are the same bits."""
+    import ctypes
+
+    import srhip._lib as L
+
+    opts = workloads.c2(0, 1, 64)[0]
+    N = srhip.Node
+    trees = srhip.random_population(29, opts, 3, np.float32, seed=12, max_size=30)
+    trees = list(trees) + [N("x3"), srhip.cos(N("x1")) * N("x2"), srhip.exp(N("x2") * N(val=1000.0))]
+    nodes, offs = srhip.flatten(trees, opts, np.float32)
+    rng = np.random.default_rng(12)
+    X = rng.standard_normal((3, 8192)).astype(np.float32)
+    y = (2 * np.cos(X[2]) + X[0] ** 2 - 2).astype(np.float32)
+    prog = srhip.Program(ctx, nodes, offs, opts, np.float32)
+    assert prog.stats()["max_stack"] <= 2
+    ds = srhip.DeviceDataset(ctx, X, y)
+    loss = srhip.L2DistLoss()
+
+    def plan():  # (an MI355X: 256 CUs, 160 KB of LDS per workgroup)
+        q = L.PlanQuery(dtype=L.F32, mode=0, nlive=32, m=8192, maxfeat=3, nd=len(prog.derived_columns()), kmax=2,
+                        dkmax=2, have_recs=1, num_cu=256, lds_max=160 * 1024)
+        out = L.PlanInfo()
+        assert L.load().srhip_plan_eval(ctypes.byref(q), ctypes.byref(out)) == 0
+        return out
+
+    p = plan()
+    assert (p.kind, p.hot, p.nrb, p.wgs, p.expect_items) == (1, 1, 4, 4, 4)
+    h0 = ctx.hot_form_launches()
+    l, ok = prog.eval_loss(ds, loss)
+    assert ctx.hot_form_launches() == h0 + 1
+    l, ok = l.copy(), ok.copy()
+    monkeypatch.setenv("SRHIP_NO_HOT_FORM", "1")
+    p = plan()
+    assert (p.kind, p.hot) == (1, 0)
+    l2, ok2 = prog.eval_loss(ds, loss)
+    assert ctx.hot_form_launches() == h0 + 1
+    assert np.array_equal(ok, ok2) and np.array_equal(_bits(l), _bits(l2))
+    assert ok[:31].any() and not ok[31]
+    prog.close()

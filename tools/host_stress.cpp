@@ -142,6 +142,26 @@ static void host_worker(int id, int rounds, const std::vector<Population>* pops)
     sums[2 * (size_t)nt + 2 * nf] = 4096.0;
     CHECK(srhip_partials_finalize(P, nf, sums.data(), chk.data(), loss.data(), ok.data(), status.data()));
     srhip_program_destroy(P);  // (background teardown)
+    // the launch decision over random shapes (srhip_plan_eval: arithmetic on sizes, no device)
+    srhip_plan_query q{};
+    q.dtype = (int32_t)(rng() % 3);
+    q.mode = (int32_t)(rng() % 2);
+    q.nlive = (int32_t)(rng() % 3000);
+    q.m = 1 + (int64_t)(rng() % 20000000);
+    q.maxfeat = (int32_t)(rng() % 40);
+    q.nd = (int32_t)(rng() % 20);
+    q.kmax = 1 + (int32_t)(rng() % 8);
+    q.dkmax = 1 + (int32_t)(rng() % 8);
+    q.weighted = (int32_t)(rng() % 2);
+    q.have_recs = 1;
+    q.num_cu = 1 + (int32_t)(rng() % 304);
+    q.lds_max = 64 * 1024 + 32 * 1024 * (int64_t)(rng() % 4);
+    srhip_plan_info pi{};
+    if (srhip_plan_eval(&q, &pi) != 0 || pi.nrb < 1 || pi.rb_rows < 256 || (pi.xlds && pi.lds > q.lds_max) ||
+        (pi.kind == 1 && pi.expect_items != pi.nrb - pi.probe_blocks - pi.tail_blocks + pi.tail_shares)) {
+      fprintf(stderr, "FAIL launch plan: kind %d nrb %d rb %d lds %lld\n", pi.kind, pi.nrb, pi.rb_rows, (long long)pi.lds);
+      g_fail = 1;
+    }
     // malformed tables: a child index past the tree, an operator index past the table
     std::vector<srhip_node> bad(p.nodes.begin(), p.nodes.begin() + p.offs[1]);
     if (!bad.empty() && bad[0].degree > 0) {
