@@ -1,7 +1,7 @@
 // srhip_internal.h — library-internal declarations shared by the translation units of libsrhip.so
-// (srhip_host.cpp: compiler, datasets, evaluation driver, C ABI; srhip_plan.cpp: the launch decision
-// and the launch order, device-free; srhip_optim.cpp: constant
-// gradients and the batched BFGS constant optimizer).  Not part of the public ABI.
+// (srhip_host.cpp: program upload, datasets, evaluation driver, C ABI; srhip_compile.cpp: the tree
+// compiler, device-free; srhip_plan.cpp: the launch decision and the launch order, device-free;
+// srhip_optim.cpp: constant gradients and the batched BFGS constant optimizer).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -21,6 +21,7 @@
 #include "srhip_isa.h"
 #include "srhip_kernels.h"
 #include "srhip_plan.h"
+#include "srhip_compile.h"
 
 namespace srhip {
 
@@ -346,15 +347,6 @@ struct View {
   int32_t nfeat_x = -1;
   int32_t nd_x = 0;  // its derived columns (then as many tangent-zero columns)
 };
-int compile_program(srhip_program& P);       // eval program (+ invalidates the gradient program)
-extern thread_local double g_patch_scan_s, g_patch_copy_s;  // optimiser timing split (SRHIP_OPTIM_TIMING), per thread
-int compile_grad_program(srhip_program& P);  // gradient program, uploaded
-void grad_derived_spec(srhip_program& P);     // P.gdspec / gdbase from the trees (once)
-// Speculative slot `slot` := tree t at constants c[0 .. nconst) (get_constants order), host side;
-// false if the tree cannot be instantiated.  *static_fail: did_succeed is false before any row is
-// evaluated (a non-finite constant leaf or constant subtree; no evaluation needed).  [lo, hi) grows by the instructions written.
-bool spec_instantiate(srhip_program& P, int32_t slot, int32_t t, const double* c, bool* static_fail, int64_t& lo,
-                      int64_t& hi);
 // sync = false: the copies stay queued on the context's stream (the caller's next evaluation, which
 // synchronises before returning, must follow before P's host code changes again)
 // stream: the copy's stream (nullptr: the context's; srhip_program_create uses the context's upload

@@ -82,6 +82,7 @@ void set_all_consts(srhip_program& P, const double* c) {
 // land at g[coff[t] ..].  The gradient program must match the program's current constants.
 // SRHIP_OPTIM_TIMING=1: host-side time split of the optimiser (compile/patch vs the rest), stderr
 static thread_local double g_t_compile = 0.0, g_t_eval = 0.0, g_t_host = 0.0;
+static thread_local double g_patch_copy_s = 0.0;  // of g_t_compile: the patched uploads (the scans: g_patch_scan_s)
 static thread_local int64_t g_n_launch = 0;
 static thread_local bool g_stats_on = false;
 static thread_local bool g_launch_log = false;  // SRHIP_OPTIM_TIMING=3: one stderr line per launch (caller's group)
@@ -501,6 +502,48 @@ static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_progra
   return eval_grad_items_on(ctx, P, be, items, timed);
 }
 
+// Instructions [lo, hi) of P's gradient program to its device copy, on ctx's stream through the pinned
+// buffer `stage` (a pageable source makes the runtime stage it synchronously).  Not synchronised: the
+// caller leaves `stage` and gcode[lo, hi) alone until the stream has passed the copy.
+static int upload_gcode(srhip_ctx* ctx, srhip_program& P, int64_t lo, int64_t hi, HostBuf& stage) {
+  if (hi <= lo) return SRHIP_OK;
+  const size_t nb = (size_t)(hi - lo) * sizeof(Ins);
+  HIP_TRY(stage.ensure(nb));
+  memcpy(stage.p, P.gcode.data() + lo, nb);
+  HIP_TRY(hipMemcpyAsync((Ins*)P.d_gcode.p + lo, stage.p, nb, hipMemcpyHostToDevice, ctx->stream));
+  return SRHIP_OK;
+}
+
+// The gradient program at P's current constants, on the device: compile_grad_host (srhip_compile.cpp)
+// decides between patch and full compile and does either; this uploads what its GradEdit names.
+static int compile_grad_program(srhip_program& P) {
+  GradEdit edit;
+  int rc = compile_grad_host(P, edit);
+  if (rc || edit.kind == GradEdit::NONE) return rc;
+  if (!P.ctx) return fail(SRHIP_ERR_INVALID, "host-only program");
+  const double t_copy0 = now_s();
+  HIP_TRY(hipSetDevice(P.ctx->device));
+  if (edit.kind == GradEdit::PATCHED) {  // the device copy differs only in [lo, hi)
+    rc = upload_gcode(P.ctx, P, edit.lo, edit.hi, P.ctx->h_gpatch);
+    if (rc) return rc;
+    // no synchronisation here: the gradient launch follows on the same stream, and eval_grad
+    // synchronises before it returns, so the staging is not touched while this copy is in flight
+    g_patch_copy_s += now_s() - t_copy0;
+  } else {
+    HIP_TRY(P.d_gcode.ensure(P.gcode.size() * sizeof(Ins)));
+    HIP_TRY(P.d_goff.ensure(std::max<size_t>(1, P.gprog_off.size()) * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(P.d_gcode.p, P.gcode.data(), P.gcode.size() * sizeof(Ins), hipMemcpyHostToDevice, P.ctx->stream));
+    if (!P.gprog_off.empty())
+      HIP_TRY(hipMemcpyAsync(P.d_goff.p, P.gprog_off.data(), P.gprog_off.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                             P.ctx->stream));
+    // the sources are the program's own vectors, which the next patch or speculative slot rewrites:
+    // both copies are complete before this returns
+    HIP_TRY(hipStreamSynchronize(P.ctx->stream));
+  }
+  P.grad_ready = true;
+  return SRHIP_OK;
+}
+
 // Loss and gradient for `trees` at the program's current constants: f[t], g[coff[t] ..], ok[t]
 // (nullable; did_succeed -- a tree can succeed with an overflowing loss: f = Inf, ok = 1), plus the
 // items in `extra` (speculative slots, already instantiated; their instructions [spec_lo, spec_hi)
@@ -521,12 +564,10 @@ static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, 
     items.push_back(GradItem{t, t, f + t, g + coff[t], ok ? ok + t : nullptr, value_only && value_only[t]});
   if (extra) items.insert(items.end(), extra->begin(), extra->end());
   auto body = [&]() -> int {
-    if (spec_hi > spec_lo) {  // pinned staging (synchronised with the launch in eval_grad_items)
-      const size_t nb = (size_t)(spec_hi - spec_lo) * sizeof(Ins);
-      HIP_TRY(ctx->h_gspec.ensure(nb));
-      memcpy(ctx->h_gspec.p, P->gcode.data() + spec_lo, nb);
-      HIP_TRY(hipMemcpyAsync((Ins*)P->d_gcode.p + spec_lo, ctx->h_gspec.p, nb, hipMemcpyHostToDevice, ctx->stream));
-    }
+    // the speculative slots, through a staging buffer of their own: a patch's copy (compile_grad_program,
+    // h_gpatch) can be in flight before the same launch; synchronised with the launch in eval_grad_items
+    const int urc = upload_gcode(ctx, *P, spec_lo, spec_hi, ctx->h_gspec);
+    if (urc) return urc;
     return eval_grad_items(ctx, ds, P, loss, v, items, timed, rb);
   };
   rc = body();

@@ -2,7 +2,7 @@
 table of exact derivatives and the trees that put every rule of csrc/srhip_grad_impl.h, in every operand
 form of csrc/srhip_grad_tile.inc, in front of it.  Not a test module.
 
-Operand forms (csrc/srhip_host.cpp emit; a gradient program has no leaf-leaf superinstructions at the
+Operand forms (csrc/srhip_compile.cpp emit; a gradient program has no leaf-leaf superinstructions at the
 build's default SRHIP_GRAD_SUPER_LEVEL, and never folds a constant subtree, whose constants need tangents):
 a binary operator whose right operand is a leaf runs as `A op X` / `A op c` after its left operand was
 left in the accumulator A (a leaf left operand is loaded into A first), one whose left operand alone is a

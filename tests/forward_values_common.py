@@ -9,7 +9,7 @@ are exact for every value, -0.0, subnormals, Inf and NaN included:
     R1(x) = cond(ones * ones, I(x))  the same value from a subtree that needs one stack slot
     NN(x) = neg(neg(x))              a subtree whose code begins with a feature load (fuses with a push)
 
-Stack slots (csrc/srhip_host.cpp emit): an operator of two subtrees evaluates the one with the larger need
+Stack slots (csrc/srhip_compile.cpp emit): an operator of two subtrees evaluates the one with the larger need
 first (the left one on a tie), pushes it to slot `base` and evaluates the other at base + 1; so a tree T sits
 at base k inside k nested cond(G, .) whose left sides G are products of ones that need as many slots as what
 they guard: cond(G(n), T) with need(T) = n evaluates G first, pushes it, runs T one slot up and returns T's

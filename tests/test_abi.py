@@ -39,6 +39,23 @@ def test_library_exports_every_declared_symbol():
         assert getattr(lib, f) is not None
 
 
+def test_device_free_units_call_no_hip_runtime():
+    """The tree compiler and the launch decision (csrc/srhip_compile.cpp, csrc/srhip_plan.cpp) are host
+    arithmetic: their objects have no undefined symbol of the HIP runtime API (hipMalloc, hipMemcpyAsync,
+    ...).  The library's own srhip:: helpers (fail, last_error, env_get, ...) are expected."""
+    import srhip._lib as L
+
+    build = os.path.dirname(L.LIB_PATH)
+    for unit in ("srhip_compile", "srhip_plan"):
+        obj = os.path.join(build, unit + ".o")
+        assert os.path.isfile(obj), f"{obj} is missing: the build makes it"
+        out = subprocess.run(["nm", "-u", obj], capture_output=True, text=True, check=True).stdout
+        undefined = [ln.split()[-1] for ln in out.splitlines() if ln.split()]
+        assert undefined, f"{unit}.o: nm lists no undefined symbol at all"
+        hip = [s for s in undefined if re.match(r"^hip[A-Z]", s)]
+        assert not hip, f"{unit}.o calls the HIP runtime: {hip}"
+
+
 def test_constants_match_header():
     import srhip._lib as L
 

@@ -207,7 +207,7 @@ def test_optimizer_outcome_vs_fd_reference_procedure(ctx, oracle):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_grad_program_patch_equals_full_compile(ctx, dtype):
     """After set_constants, the gradient program recompiles only the trees whose constants moved
-    (in place, srhip_host.cpp patch_grad_t); its losses, gradients and masks equal, bit for bit, a
+    (in place, srhip_compile.cpp patch_grad_t); its losses, gradients and masks equal, bit for bit, a
     fresh program compiled in full with the same constants — including a tree whose new constant
     is NaN (a static did_succeed failure), a second patch on top of the first, and that tree patched
     back into its kept slot once its constants are finite again."""

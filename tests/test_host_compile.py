@@ -88,7 +88,7 @@ def test_host_pool_back_to_back_jobs_from_many_threads():
 
 
 def test_code_cache_hits_equal_fresh_compiles(tmp_path, monkeypatch):
-    """The per-tree code cache (csrc/srhip_host.cpp CodeCache): a population compiled from cached
+    """The per-tree code cache (csrc/srhip_compile.cpp CodeCache): a population compiled from cached
     entries (second compile of the same trees, and a population mixing cached and new trees) has
     exactly the instructions (handler, operand, immediate), stack needs and costs of a compile with the
     cache off -- plain and derived programs -- and the superinstruction switch is part of the key."""

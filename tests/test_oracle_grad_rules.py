@@ -247,7 +247,7 @@ def test_device_rule_programs_compile_on_the_host(dt):
     evaluator's program only), and this change adds no ABI for it.  What the node tables do show is
     asserted: the population holds, for every unary operator whose rule is not inline, that operator
     applied to feature x1 in a tree with a constant -- the nodes a constant-gradient launch turns into
-    derived columns (csrc/srhip_host.cpp grad_derived_spec), 24 distinct ones, within the view's 32."""
+    derived columns (csrc/srhip_compile.cpp grad_derived_spec), 24 distinct ones, within the view's 32."""
     import srhip as sr
 
     T = NP[dt]

@@ -1,12 +1,13 @@
 // host_stress.cpp — concurrency / memory stress of libsrhip's host C++ through the C ABI, the driver the
 // sanitizer builds run (SURVEY.md 5 sanitizers row; the reference's CI runs --check-bounds=yes,
 // .github/workflows/CI.yml:72).  `make -C tools asan` / `make -C tools tsan` link it against a libsrhip
-// whose host objects (srhip_host.cpp, srhip_batch.cpp, srhip_optim.cpp, srhip_comm.cpp) are built with
+// whose host objects (srhip_host.cpp, srhip_compile.cpp, srhip_plan.cpp, srhip_batch.cpp, srhip_optim.cpp,
+// srhip_comm.cpp) are built with
 // -fsanitize=address,undefined / -fsanitize=thread (on the host side only: -Xarch_host), the sanitizer
 // runtime linked into this executable -- no LD_PRELOAD.
 //
 // Host phase (no GPU needed): THREADS threads compile host-only programs (ctx = NULL) of random
-// populations at once -- the persistent host pool, the 64-shard code cache with its first-sighting
+// populations at once (srhip_compile.cpp) -- the persistent host pool, the 64-shard code cache with its first-sighting
 // table (populations recur, so trees are cached on their second sighting and hit from their third),
 // background teardown -- query and set constants, run srhip_partials_finalize over random partials,
 // and feed malformed node tables (bad children, bad operator indices) that must fail cleanly.
