@@ -205,6 +205,45 @@ int srhip_eval_loss_wait(srhip_eval_ticket* ticket, double* out_loss, uint8_t* o
 int srhip_eval_predict(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog,
                        const int64_t* idx, int64_t nidx, void* out_pred, uint8_t* out_ok);
 
+/* ---- elementwise losses given as expressions (the reference's loss::Function branches of _loss /
+ * _weighted_loss, src/LossFunctions.jl:13-33: any l(prediction, target[, weight])) ---------------------
+ * A loss l(prediction, target[, weight]) as one Node tree over an operator table.
+ * Feature 1 = prediction, 2 = target, 3 = weight (nargs = 3 only).  Constants are val.
+ * dtype: SRHIP_F32 / SRHIP_F64 (SRHIP_I32: SRHIP_ERR_UNSUPPORTED).  No device is needed.
+ * Operators mean what they mean in a tree of the population (csrc/srhip_ops.h FOps<T>): ^ is safe_pow
+ * (NaN for a negative base with a non-integer exponent, ...), log is safe_log (NaN at x <= 0), sqrt is
+ * safe_sqrt, and so on -- not the Julia Base functions, which throw there.  Every value is computed in T.
+ * Limits, each SRHIP_ERR_INVALID with a message naming it: at most 64 nodes (counting a shared subtree
+ * once per use); a stack need of at most 8 (every leaf takes a slot, the child of greater need is
+ * evaluated first, two children of equal need cost one slot more); feature indices in 1..nargs; operator
+ * indices inside the table; finite constants (in T). */
+typedef struct srhip_loss_expr srhip_loss_expr;
+int srhip_loss_expr_create(int dtype, const srhip_node* nodes, int64_t nnodes, const srhip_operators* ops,
+                           int32_t nargs, srhip_loss_expr** out);
+void srhip_loss_expr_destroy(srhip_loss_expr* e);
+/* The per-row values l(pred[i], y[i][, w[i]]) in T, computed on the host with the operator bodies of
+ * csrc/srhip_ops.h.  w may be NULL for nargs = 2.  No device is needed. */
+int srhip_loss_expr_eval_host(const srhip_loss_expr* e, const void* pred, const void* y, const void* w,
+                              int64_t n, void* out);
+/* srhip_eval_loss with the loss given as an expression: the evaluation of srhip_eval_predict with the
+ * predictions left on the device, then one loss pass over them for the trees that succeeded.
+ * out_ok[t] = did_succeed of the evaluation, srhip_eval_predict's decision.
+ * out_loss[t] = +Inf where !ok, else sum_i l_i / m (unweighted dataset) or sum_i l_i / sum_i w_i (weighted),
+ * every l_i in T, the sums in double.  A non-finite l_i is no failure: it propagates into out_loss[t] (NaN
+ * or +-Inf) with out_ok[t] = 1, as a Julia closure's would.  out_loss[t] depends on tree t's predictions,
+ * the rows and the expression only (fixed summation order: blocks of srhip_lossx_block_rows() rows): the
+ * same bits alone or among others, at any position, beside failed trees.
+ * A weighted dataset needs nargs = 3, an unweighted one nargs = 2, program and expression the same dtype
+ * (SRHIP_ERR_INVALID); an Int32 program is SRHIP_ERR_UNSUPPORTED.  The predictions of the whole program
+ * stay resident: ntrees * m * sizeof(T) bytes above SRHIP_LOSSX_MAX_BYTES (environment, read per call,
+ * default 8 GiB) is SRHIP_ERR_NOMEM -- split the population.  srhip_last_kernel_ms reports the loss pass
+ * (< 0 when no tree succeeded: no loss launch), srhip_last_work what the prediction launch counted. */
+int srhip_eval_loss_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog,
+                         const srhip_loss_expr* e, const int64_t* idx, int64_t nidx,
+                         double* out_loss, uint8_t* out_ok);
+/* Rows of one block of the loss pass's summation (a compile-time constant of the library). */
+int32_t srhip_lossx_block_rows(void);
+
 /* Convenience: program_create + eval_loss + program_destroy. */
 int srhip_eval_loss_batch(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_node* nodes,
                           const int64_t* tree_offsets, int32_t ntrees, const srhip_operators* ops,

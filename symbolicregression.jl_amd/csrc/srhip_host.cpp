@@ -26,6 +26,7 @@
 #include "srhip_internal.h"
 #include "srhip_isa.h"
 #include "srhip_kernels.h"
+#include "srhip_lossx.h"
 
 using namespace srhip;
 
@@ -792,7 +793,8 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
     dp->used = true;
     dp->stride = stride;
   }
-  if (mode == MODE_PRED)
+  // (no host output asked for: srhip_eval_loss_expr reads the predictions where they are, J.pred)
+  if (mode == MODE_PRED && out_pred)
     HIP_TRY(hipMemcpyAsync(out_pred, pred.p, (size_t)nt * v.m * es, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipEventRecord(rs->done, ctx->stream));
   return SRHIP_OK;
@@ -1797,6 +1799,73 @@ int srhip_eval_predict(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_prog
                        int64_t nidx, void* out_pred, uint8_t* out_ok) {
   if (!out_pred || !out_ok) return fail(SRHIP_ERR_INVALID, "null output");
   return run_eval(ctx, ds, prog, MODE_PRED, nullptr, idx, nidx, nullptr, out_pred, out_ok);
+}
+
+// srhip_eval_loss with the loss given as an expression: the prediction evaluation of srhip_eval_predict
+// with its output left on the device (the job's EvalJob::pred, alive until this function returns), the
+// did_succeed decisions as they are, then the loss pass (srhip_lossx.hip) over the trees that succeeded.
+int srhip_eval_loss_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog, const srhip_loss_expr* e,
+                         const int64_t* idx, int64_t nidx, double* out_loss, uint8_t* out_ok) {
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  if (!out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null output");
+  int rc = check_eval_args(ctx, ds, prog, MODE_PRED, nullptr);
+  if (rc) return rc;
+  if (prog->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "loss expressions are Float32 / Float64 only (Int32 program)");
+  if (prog->dtype != e->prog.dtype)
+    return fail(SRHIP_ERR_INVALID, "loss expression dtype %d != program dtype %d", e->prog.dtype, prog->dtype);
+  if (!ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
+  if (ds->weighted != (e->prog.nargs == 3))
+    return fail(SRHIP_ERR_INVALID, "a%s dataset needs a loss expression of nargs = %d (this one has nargs = %d)",
+                ds->weighted ? " weighted" : "n unweighted", ds->weighted ? 3 : 2, (int)e->prog.nargs);
+  const int32_t nt = prog->ntrees;
+  const int64_t m = idx ? nidx : ds->n;
+  // the whole population's predictions stay resident for the loss pass
+  long long cap = 8LL << 30;
+  if (const char* c = env_get("SRHIP_LOSSX_MAX_BYTES"))
+    if (*c) cap = atoll(c);
+  const long double need = (long double)nt * (long double)std::max<int64_t>(m, 0) * (long double)dtype_size(prog->dtype);
+  if (need > (long double)cap)
+    return fail(SRHIP_ERR_NOMEM, "loss expression: the prediction buffer needs %.0Lf bytes (%d trees x %lld rows), above the cap "
+                "SRHIP_LOSSX_MAX_BYTES = %lld bytes; evaluate the population in parts", need, (int)nt, (long long)m, cap);
+  RunJob R;
+  R.J.rs = &ctx->rs[0];
+  rc = run_issue(ctx, ds, prog, MODE_PRED, nullptr, idx, nidx, nullptr, R);
+  if (rc) return rc;
+  if (R.J.launched) {
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+  }
+  rc = run_complete(ctx, R, nullptr, out_ok);
+  if (rc) return rc;
+  ctx->timed = false;  // srhip_last_kernel_ms reports the loss pass; none: < 0
+  std::vector<int32_t> live;
+  for (int32_t t = 0; t < nt; ++t) {
+    out_loss[t] = INFINITY;
+    if (out_ok[t]) live.push_back(t);
+  }
+  if (live.empty()) return SRHIP_OK;
+  const View& v = R.v;
+  const int32_t nl = (int32_t)live.size(), nslots = nl + (ds->weighted ? 1 : 0);
+  const int64_t nblocks = lossx_blocks(v.m);
+  // [partials | out | list]
+  const size_t o_out = (size_t)nslots * nblocks * sizeof(double), o_list = o_out + (size_t)nslots * sizeof(double);
+  HIP_TRY(ctx->lossx_work.ensure(o_list + (size_t)nl * sizeof(int32_t)));
+  uint8_t* const wp = (uint8_t*)ctx->lossx_work.p;
+  HIP_TRY(hipMemcpyAsync(wp + o_list, live.data(), (size_t)nl * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  HIP_TRY(launch_lossx(e->prog, R.J.pred.p, v.y, ds->weighted ? v.w : nullptr, v.m, (const int32_t*)(wp + o_list), nl,
+                       (double*)wp, (double*)(wp + o_out), ctx->stream));
+  HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+  std::vector<double> sums(nslots);
+  HIP_TRY(hipMemcpyAsync(sums.data(), wp + o_out, (size_t)nslots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  rc = stream_wait(ctx);
+  if (rc) return rc;
+  ctx->last_ev0 = ctx->ev0;
+  ctx->last_ev1 = ctx->ev1;
+  ctx->timed = true;
+  const double den = ds->weighted ? sums[nl] : (double)v.m;
+  for (int32_t s = 0; s < nl; ++s) out_loss[live[s]] = sums[s] / den;
+  return SRHIP_OK;
 }
 
 int srhip_eval_loss_batch(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_node* nodes, const int64_t* offsets,

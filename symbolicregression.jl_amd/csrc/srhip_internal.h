@@ -223,6 +223,7 @@ struct srhip_ctx {
   bool block_ctr_dirty = false;
   srhip::DevBuf slab_rows;  // [row block][order slot] valid rows evaluated
   srhip::DevBuf d_ulist;    // the device's undecided-tree list ([0] = count; reset by its consumer)
+  srhip::DevBuf lossx_work; // srhip_eval_loss_expr's loss pass: [block partials | per-slot sums | tree list]
   // work of the last srhip_eval_loss / srhip_eval_predict on this context (srhip_last_work):
   // evaluated node-rows, nominal node-rows (every live tree on every row), evaluated operator-node
   // rows, evaluated tree-rows

@@ -34,6 +34,7 @@ from .api import (
 from .dataset import Dataset
 from .device import (Coalescer, Context, DeviceDataset, Program, device_count, get_context, isa_handler_count,
                      isa_handler_name, isa_handler_ok)
+from .loss_expr import ExprLoss
 from .losses import (
     DWDMarginLoss,
     ExpLoss,

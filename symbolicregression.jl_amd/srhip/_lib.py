@@ -103,6 +103,12 @@ SIGNATURES = {
     "srhip_eval_loss": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, _vp, _vp]),
     "srhip_eval_loss_rowsets": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _vp, _vp, _vp]),
     "srhip_eval_predict": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "srhip_loss_expr_create": (ctypes.c_int, [ctypes.c_int, _vp, _i64, ctypes.POINTER(Operators), _i32,
+                                              ctypes.POINTER(_vp)]),
+    "srhip_loss_expr_destroy": (None, [_vp]),
+    "srhip_loss_expr_eval_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "srhip_eval_loss_expr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "srhip_lossx_block_rows": (_i32, []),
     "srhip_eval_loss_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, ctypes.POINTER(_vp)]),
     "srhip_eval_loss_wait": (ctypes.c_int, [_vp, _vp, _vp]),
     "srhip_eval_loss_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, ctypes.POINTER(Operators),

@@ -16,11 +16,13 @@ Same argument meaning and error behaviour as the reference; there is no CPU fall
 from __future__ import annotations
 
 import inspect
+import os
 
 import numpy as np
 
 from .dataset import Dataset
 from .device import Program, get_context
+from .loss_expr import ExprLoss
 from .losses import is_device_loss
 from .node import Node, count_nodes, flatten
 
@@ -161,9 +163,33 @@ def eval_loss_rowsets_batch(trees, dataset: Dataset, options, idxs, regularizati
     return out, ok
 
 
+def _lossx_max_trees(dataset: Dataset, idx) -> int:
+    """Trees whose predictions fit srhip_eval_loss_expr's resident buffer (SRHIP_LOSSX_MAX_BYTES, default
+    8 GiB): a larger population is evaluated in programs of that many."""
+    cap = int(os.environ.get("SRHIP_LOSSX_MAX_BYTES") or (8 << 30))
+    m = dataset.n if idx is None else len(idx)
+    return max(1, cap // max(1, m * dataset.X.dtype.itemsize))
+
+
 def _eval_loss_batch_device(trees, dataset: Dataset, options, idx):
     ctx = _ctx(options)
     loss = options.elementwise_loss
+    if isinstance(loss, ExprLoss):
+        # the expression runs on the device over predictions that stay there; every tree's loss is the
+        # same bits in any split
+        step = _lossx_max_trees(dataset, idx)
+        outs, oks = [], []
+        for b in range(0, len(trees), step):
+            prog = compile_trees(trees[b:b + step], options, dataset.X.dtype)
+            try:
+                o, k = prog.eval_loss(dataset.device(ctx), loss, idx)
+            finally:
+                prog.close()
+            outs.append(o)
+            oks.append(k)
+        if not outs:
+            return np.zeros(0), np.zeros(0, dtype=bool)
+        return np.concatenate(outs), np.concatenate(oks)
     prog = compile_trees(trees, options, dataset.X.dtype)
     try:
         if is_device_loss(loss):

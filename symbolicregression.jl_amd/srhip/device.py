@@ -202,10 +202,18 @@ class Program:
         return out
 
     def eval_loss(self, ds: DeviceDataset, loss, idx=None):
+        """srhip_eval_loss for a built-in loss; an ExprLoss goes to srhip_eval_loss_expr (the loss expression
+        evaluated on the device over predictions that stay there)."""
+        from .loss_expr import ExprLoss
+
         out = np.empty(self.ntrees, dtype=np.float64)
         ok = np.empty(self.ntrees, dtype=np.uint8)
-        ls = loss.c_struct()
         idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        if isinstance(loss, ExprLoss):
+            check(_lib.load().srhip_eval_loss_expr(self.ctx.handle, ds.handle, self.handle, loss.handle(self.dtype),
+                                                   ptr(idxa), 0 if idxa is None else len(idxa), ptr(out), ptr(ok)))
+            return out, ok.astype(bool)
+        ls = loss.c_struct()
         check(_lib.load().srhip_eval_loss(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls), ptr(idxa),
                                           0 if idxa is None else len(idxa), ptr(out), ptr(ok)))
         return out, ok.astype(bool)

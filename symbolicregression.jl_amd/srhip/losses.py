@@ -6,7 +6,8 @@ reference's ``_loss`` / ``_weighted_loss`` (src/LossFunctions.jl:13-33) and list
 Each class carries its device kind code; the device computes the loss per row in T and
 reduces it (fused into the evaluation kernel).  A plain Python callable ``f(pred, target)``
 (or ``f(pred, target, w)``) is also accepted as ``elementwise_loss``: predictions then come from
-the device and the callable runs on the host, like a user-defined Julia loss in the reference.
+the device and the callable runs on the host, like a user-defined Julia loss in the reference.  The same
+loss written as an expression (``srhip.ExprLoss``, srhip/loss_expr.py) is evaluated on the device.
 """
 from __future__ import annotations
 
