@@ -387,6 +387,33 @@ int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srh
                                     double* starts_out, double* out_loss, uint8_t* out_improved,
                                     int64_t* out_fcalls);
 
+/* srhip_eval_loss_grad with the loss given as an expression (srhip_loss_expr): the same dual-number launch
+ * over (tree, constant chunk) pairs, its loss stage running the expression's program over dual numbers with
+ * one tangent, d / d prediction (every operator's value and partials are the ones the trees' own operators
+ * use).  out_ok[t] is srhip_eval_loss_grad's decision for the tree -- the expression's outputs take no part
+ * in it.  Where it is 0: out_loss[t] = +Inf and the tree's gradient slice is 0.  Elsewhere out_loss[t] =
+ * sum_i l_i / m (unweighted dataset) or / sum_i w_i (weighted; the expression names the weight itself, the
+ * kernel does not multiply by it), and the slice is sum_i dl_i * d pred_i / d c_k over the same denominator,
+ * every l_i, dl_i and product in T, the sums in double in the fixed order of srhip_eval_loss_grad (the same
+ * bits alone or among others).  A non-finite result is passed through with ok = 1.  For square(p - t) and
+ * w * square(p - t) the results have the bits of srhip_eval_loss_grad under SRHIP_LOSS_L2.
+ * Argument errors as srhip_eval_loss_expr; srhip_last_kernel_ms reports the gradient kernels. */
+int srhip_eval_loss_grad_expr(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* prog,
+                              const srhip_loss_expr* e, const int64_t* idx, int64_t nidx,
+                              double* out_loss, double* out_grad, uint8_t* out_ok);
+/* srhip_optimize_constants_starts under a loss expression.  Baseline and final re-score are
+ * srhip_eval_loss_expr's (out_loss[t] has its bits on the returned constants); the objective is
+ * srhip_eval_loss_grad_expr's kernel.  Inside the optimiser an objective value that is not finite (NaN or
+ * +-Inf) counts as +Inf before the line search or the acceptance test sees it (LineSearches' BackTracking
+ * shrinks on !isfinite); everything else -- methods, restarts, starts_in / starts_out, acceptance,
+ * out_fcalls -- is srhip_optimize_constants_starts.  Argument errors as srhip_eval_loss_expr; a failed
+ * call leaves prog's constants unchanged. */
+int srhip_optimize_constants_expr(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* prog,
+                                  const srhip_loss_expr* e, const int64_t* idx, int64_t nidx,
+                                  const srhip_optim_options* opt, const double* starts_in,
+                                  double* starts_out, double* out_loss, uint8_t* out_improved,
+                                  int64_t* out_fcalls);
+
 /* srhip_eval_loss_grad with one row subset per tree (row_offsets / rows as srhip_eval_loss_rowsets:
  * 0-based rows, duplicates allowed, sets may differ in length; empty sets, non-monotone offsets,
  * out-of-range rows and null pointers are SRHIP_ERR_INVALID naming the tree and the position; Int32

@@ -368,6 +368,22 @@ int srhip::check_eval_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_
   return SRHIP_OK;
 }
 
+// the argument checks the entry points that take a loss expression share (srhip_eval_loss_expr,
+// srhip_eval_loss_grad_expr, srhip_optimize_constants_expr)
+int srhip::check_loss_expr_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss_expr* e) {
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  const int rc = check_eval_args(ctx, ds, P, MODE_PRED, nullptr);
+  if (rc) return rc;
+  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "loss expressions are Float32 / Float64 only (Int32 program)");
+  if (P->dtype != e->prog.dtype)
+    return fail(SRHIP_ERR_INVALID, "loss expression dtype %d != program dtype %d", e->prog.dtype, P->dtype);
+  if (!ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
+  if (ds->weighted != (e->prog.nargs == 3))
+    return fail(SRHIP_ERR_INVALID, "a%s dataset needs a loss expression of nargs = %d (this one has nargs = %d)",
+                ds->weighted ? " weighted" : "n unweighted", ds->weighted ? 3 : 2, (int)e->prog.nargs);
+  return SRHIP_OK;
+}
+
 // run_eval's device-decided precise pass: the reduction lists the trees whose overflow bound needs
 // the precise pass, and the precise launch + its reduction follow on the stream before the one host
 // synchronisation (no host round trip between the main launch and the precise pass)
@@ -1808,15 +1824,8 @@ int srhip_eval_loss_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pr
                          const int64_t* idx, int64_t nidx, double* out_loss, uint8_t* out_ok) {
   if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
   if (!out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null output");
-  int rc = check_eval_args(ctx, ds, prog, MODE_PRED, nullptr);
+  int rc = check_loss_expr_args(ctx, ds, prog, e);
   if (rc) return rc;
-  if (prog->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "loss expressions are Float32 / Float64 only (Int32 program)");
-  if (prog->dtype != e->prog.dtype)
-    return fail(SRHIP_ERR_INVALID, "loss expression dtype %d != program dtype %d", e->prog.dtype, prog->dtype);
-  if (!ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
-  if (ds->weighted != (e->prog.nargs == 3))
-    return fail(SRHIP_ERR_INVALID, "a%s dataset needs a loss expression of nargs = %d (this one has nargs = %d)",
-                ds->weighted ? " weighted" : "n unweighted", ds->weighted ? 3 : 2, (int)e->prog.nargs);
   const int32_t nt = prog->ntrees;
   const int64_t m = idx ? nidx : ds->n;
   // the whole population's predictions stay resident for the loss pass

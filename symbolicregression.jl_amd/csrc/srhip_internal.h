@@ -364,6 +364,9 @@ int next_fail_epoch(srhip_ctx* ctx, int64_t n, int32_t** flags, int32_t* epoch);
 int check_eval_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode, const srhip_loss* loss);
 int run_eval(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode, const srhip_loss* loss,
              const int64_t* idx, int64_t nidx, double* out_loss, void* out_pred, uint8_t* out_ok);
+// check_eval_args for an entry point whose loss is an expression: dtype (Int32: unsupported), y, and the
+// dataset's weights against the expression's nargs
+int check_loss_expr_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss_expr* e);
 // The precise did_succeed pass for undecided trees (exact per-operator-node sums over the view), on the
 // evaluation program or (grad = true) on the gradient program: out_ok[u] for trees[u].
 int precise_decide(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const View& v,

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "srhip_grad.h"
+#include "srhip_grad_lossx.h"
 #include "srhip_internal.h"
 
 using namespace srhip;
@@ -187,7 +188,7 @@ struct ViewBackend {
   srhip_ctx* ctx;
   const srhip_dataset* ds;
   srhip_program* P;
-  const srhip_loss* loss;
+  LossSel loss;  // built-in kind, or an expression program
   const View& v;
   LaunchPlan L[2] = {};
   std::vector<double> sums;  // decision inputs: only the feature statistics and the row count are read
@@ -267,10 +268,15 @@ struct ViewBackend {
     a.rb_rows = Lp.rb_rows;
     a.nrb = Lp.nrb;
     a.chunks_per_group = Lp.tpg;
-    a.loss_kind = loss->kind;
-    a.loss_p0 = loss->p0;
+    a.loss_kind = loss.kind ? loss.kind->kind : 0;  // (an expression: its program travels beside these arguments)
+    a.loss_p0 = loss.kind ? loss.kind->p0 : 0.0;
     a.weighted = weighted ? 1 : 0;
     a.max_steps = P->gmax_len;
+    // the kernel by the loss selector: grad_kernel, or grad_lossx_kernel with the same arguments and grid
+    auto launch_k = [&](int kt, const GradArgs& ga, dim3 grid) {
+      return loss.expr ? launch_grad_lossx(dtype, K, kt, ga, *loss.expr, grid, ctx->stream)
+                       : launch_grad(dtype, K, kt, ga, grid, ctx->stream);
+    };
     if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));  // srhip_last_kernel_ms: the gradient kernels
     // value-only screening (SRHIP_GRAD_SCREEN = the fewest value-only chunks screened; default 0 =
     // off): row block 0 of every chunk first, in a launch of its own, then the other blocks, where a
@@ -284,12 +290,12 @@ struct ViewBackend {
       GradArgs sa = a;
       const int tpg_s = 2 * GRAD_WAVES;
       sa.chunks_per_group = tpg_s;
-      HIP_TRY(launch_grad(dtype, K, 0, sa, dim3(1, (nch + tpg_s - 1) / tpg_s), ctx->stream));
+      HIP_TRY(launch_k(0, sa, dim3(1, (nch + tpg_s - 1) / tpg_s)));
       a.block0 = 1;
       a.screened = 1;
-      HIP_TRY(launch_grad(dtype, K, 0, a, dim3(Lp.nrb - 1, Lp.groups), ctx->stream));
+      HIP_TRY(launch_k(0, a, dim3(Lp.nrb - 1, Lp.groups)));
     } else {
-      HIP_TRY(launch_grad(dtype, K, ps.kt, a, dim3(Lp.nrb, Lp.groups), ctx->stream));
+      HIP_TRY(launch_k(ps.kt, a, dim3(Lp.nrb, Lp.groups)));
     }
     // the reduction writes the records straight into coherent pinned host memory (no copy on the stream)
     HIP_TRY(launch_grad_reduce(dtype, ps.kt, (const double*)ctx->g_slab.p, Lp.nrb, nch, (double*)ctx->h_gred[pi].p,
@@ -318,7 +324,7 @@ struct RowsetBackend {
   srhip_ctx* ctx;
   const srhip_dataset* ds;
   srhip_program* P;
-  const srhip_loss* loss;
+  LossSel loss;  // built-in kind, or an expression program
   const RowsetBatch& rb;
   int max_ld[2] = {0, 0};
   std::vector<double> sums;
@@ -367,8 +373,8 @@ struct RowsetBackend {
     a.nchunks = nch;
     a.nfeat = (int32_t)ds->nfeat;
     a.gd_nd = 0;
-    a.loss_kind = loss->kind;
-    a.loss_p0 = loss->p0;
+    a.loss_kind = loss.kind->kind;  // (built-in kinds only: eval_grad_items)
+    a.loss_p0 = loss.kind->p0;
     a.weighted = ds->weighted ? 1 : 0;
     a.max_steps = P->gmax_len;
     if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));
@@ -492,9 +498,10 @@ static int eval_grad_items_on(srhip_ctx* ctx, srhip_program* P, Backend& be, con
   return SRHIP_OK;
 }
 // on the view's rows, or (rb given: it replaces the view) every item on its tree's own row set
-static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss,
                            const View& v, const std::vector<GradItem>& items, bool timed, const RowsetBatch* rb) {
   if (rb) {
+    if (!loss.kind) return fail(SRHIP_ERR_UNSUPPORTED, "row sets under a loss expression");
     RowsetBackend be{ctx, ds, P, loss, *rb};
     return eval_grad_items_on(ctx, P, be, items, timed);
   }
@@ -548,7 +555,7 @@ static int compile_grad_program(srhip_program& P) {
 // (nullable; did_succeed -- a tree can succeed with an overflowing loss: f = Inf, ok = 1), plus the
 // items in `extra` (speculative slots, already instantiated; their instructions [spec_lo, spec_hi)
 // are uploaded with the launch).
-static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss, const View& v,
+static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss, const View& v,
                      const std::vector<int32_t>& trees, const std::vector<int64_t>& coff, double* f, double* g,
                      uint8_t* ok = nullptr, const std::vector<GradItem>* extra = nullptr, int64_t spec_lo = 0,
                      int64_t spec_hi = -1, const uint8_t* value_only = nullptr, bool timed = true,
@@ -666,7 +673,7 @@ int ls_update(LineSearch& L, double phi) {
 // the launch they are consumed in order for as long as the line search really asks for exactly that
 // alpha (same line search, bitwise-equal alpha), so every consumed result is the one the sequential
 // pipeline would have launched for: trajectories, outcomes and objective-call counts are unchanged.
-static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss,
                           const View& v, const std::vector<int32_t>& trees, const std::vector<int64_t>& coff,
                           int iterations, double g_tol, const std::vector<std::vector<double>>& starts,
                           std::vector<double>& best_x, std::vector<double>& best_f, std::vector<int64_t>& fcalls,
@@ -994,6 +1001,15 @@ static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program
     int rc = eval_grad(ctx, ds, P, loss, v, act, coff, fe.data(), ge.data(), nullptr, &sitems, spec_lo, spec_hi,
                        vonly.data(), /*timed=*/false, rb);
     if (rc) return rc;
+    if (loss.expr) {
+      // an expression's loss is no failure where it is not finite (did_succeed is the tree's alone), so NaN and
+      // -Inf reach here: they count as +Inf before the line search or the acceptance sees them (ls_update
+      // compares with >, which a NaN would pass; BackTracking shrinks on !isfinite)
+      for (int32_t t : act)
+        if (!std::isfinite(fe[t])) fe[t] = INFINITY;
+      for (double& sfv : sf)
+        if (!std::isfinite(sfv)) sfv = INFINITY;
+    }
     if (g_stats_on)  // SRHIP_OPTIM_TIMING=2: launch-size histogram
       g_hist[act.size() <= 1 ? 0 : act.size() <= 4 ? 1 : act.size() <= 16 ? 2 : act.size() <= 64 ? 3 : 4] += 1;
     const double t2 = now_s();
@@ -1195,7 +1211,7 @@ std::vector<srhip_ctx*> aux_ctxs(srhip_ctx* ctx, int n) {
 // turnaround (decisions, constant patches, synchronisation) then overlaps the other groups' kernels.
 // A tree's trajectory does not depend on the trees that share its launches (fixed row blocks, fixed
 // reduction order), so the outcome is the one bfgs_pipelined gives over all trees at once.
-int optimize_split(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss, const View& v,
+int optimize_split(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss, const View& v,
                    const std::vector<int32_t>& trees, const std::vector<int64_t>& coff, int iterations, double g_tol,
                    const std::vector<std::vector<double>>& starts, std::vector<double>& best_x,
                    std::vector<double>& best_f, std::vector<int64_t>& fcalls) {
@@ -1355,21 +1371,20 @@ void report_fcalls(const std::vector<int64_t>& fcalls, const uint8_t* out_improv
 
 }  // namespace
 
-extern "C" {
-
-int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P,
-                                    const srhip_loss* loss, const int64_t* idx, int64_t nidx,
-                                    const srhip_optim_options* opt, const double* starts_in, double* starts_out,
-                                    double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
-  if (!opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
-  int rc = check_optim_args(ctx, ds, P, loss, opt);
-  if (rc) return rc;
+// srhip_optimize_constants_starts / _expr after their argument checks: `score` is the evaluator of the loss
+// (run_eval for a built-in kind, srhip_eval_loss_expr for an expression) for the baseline and the final
+// re-score, `loss` the optimiser's objective.
+template <class Score>
+int optimize_starts(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss, Score score,
+                    const int64_t* idx, int64_t nidx, const srhip_optim_options* opt, const double* starts_in,
+                    double* starts_out, double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
+  int rc;
   HIP_TRY(hipSetDevice(ctx->device));
   const int32_t nt = P->ntrees;
   // baseline = f(tree) with the evaluator itself (src/ConstantOptimization.jl:49)
   std::vector<double> base(nt);
   std::vector<uint8_t> base_ok(nt);
-  rc = run_eval(ctx, ds, P, MODE_LOSS, loss, idx, nidx, base.data(), nullptr, base_ok.data());
+  rc = score(base.data(), base_ok.data());
   if (rc) return rc;
   View v;
   rc = make_view(ctx, ds, idx, nidx, true, v);
@@ -1434,9 +1449,77 @@ int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srh
   if (rc) return rc;
   // the loss of the returned trees, by the evaluator (the reference re-scores accepted members)
   std::vector<uint8_t> ok(nt);
-  rc = run_eval(ctx, ds, P, MODE_LOSS, loss, idx, nidx, out_loss, nullptr, ok.data());
-  if (rc) return rc;
+  rc = score(out_loss, ok.data());
+  if (rc) {
+    if (loss.expr) {  // a failed call leaves the constants as they came
+      const std::string msg = last_error();
+      restore_constants(*P, x0);
+      return fail(rc, "%s", msg.c_str());
+    }
+    return rc;
+  }
   report_fcalls(fcalls, out_improved, out_fcalls);
+  return SRHIP_OK;
+}
+
+extern "C" {
+
+int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P,
+                                    const srhip_loss* loss, const int64_t* idx, int64_t nidx,
+                                    const srhip_optim_options* opt, const double* starts_in, double* starts_out,
+                                    double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
+  if (!opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
+  const int rc = check_optim_args(ctx, ds, P, loss, opt);
+  if (rc) return rc;
+  auto score = [&](double* l, uint8_t* ok) { return run_eval(ctx, ds, P, MODE_LOSS, loss, idx, nidx, l, nullptr, ok); };
+  return optimize_starts(ctx, ds, P, LossSel(loss), score, idx, nidx, opt, starts_in, starts_out, out_loss, out_improved,
+                         out_fcalls);
+}
+
+// srhip_optimize_constants_starts under a loss expression: baseline and re-score by srhip_eval_loss_expr,
+// the objective by grad_lossx_kernel
+int srhip_optimize_constants_expr(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss_expr* e,
+                                  const int64_t* idx, int64_t nidx, const srhip_optim_options* opt,
+                                  const double* starts_in, double* starts_out, double* out_loss,
+                                  uint8_t* out_improved, int64_t* out_fcalls) {
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  if (!opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
+  if (opt->iterations < 0 || opt->nrestarts < 0) return fail(SRHIP_ERR_INVALID, "negative iterations / restarts");
+  const int rc = check_loss_expr_args(ctx, ds, P, e);
+  if (rc) return rc;
+  auto score = [&](double* l, uint8_t* ok) { return srhip_eval_loss_expr(ctx, ds, P, e, idx, nidx, l, ok); };
+  return optimize_starts(ctx, ds, P, LossSel(&e->prog), score, idx, nidx, opt, starts_in, starts_out, out_loss,
+                         out_improved, out_fcalls);
+}
+
+// srhip_eval_loss_grad under a loss expression: the same view, decisions and reduction, the loss stage of
+// every launch running the expression's program (srhip_grad_lossx.hip)
+int srhip_eval_loss_grad_expr(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss_expr* e,
+                              const int64_t* idx, int64_t nidx, double* out_loss, double* out_grad, uint8_t* out_ok) {
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  if (!out_loss || !out_grad || !out_ok) return fail(SRHIP_ERR_INVALID, "null output");
+  int rc = check_loss_expr_args(ctx, ds, P, e);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  View v;
+  rc = make_view(ctx, ds, idx, nidx, true, v);
+  if (rc) return rc;
+  if (idx && ds->weighted) {
+    rc = gathered_weight_sum(ctx, ds, nidx, v);
+    if (rc) return rc;
+  }
+  rc = derived_view(ctx, ds, P, v);
+  if (rc) return rc;
+  const std::vector<int64_t> coff = const_offsets(*P);
+  std::vector<int32_t> all(P->ntrees);
+  for (int32_t t = 0; t < P->ntrees; ++t) all[t] = t;
+  rc = eval_grad(ctx, ds, P, LossSel(&e->prog), v, all, coff, out_loss, out_grad, out_ok);
+  if (rc) return rc;
+  for (int32_t t = 0; t < P->ntrees; ++t)  // a failed tree: +Inf and a zero slice, whatever its rows summed to
+    if (!out_ok[t]) {
+      out_loss[t] = INFINITY;
+      std::fill(out_grad + coff[t], out_grad + coff[t + 1], 0.0);
+    }
   return SRHIP_OK;
 }
 

@@ -125,6 +125,9 @@ SIGNATURES = {
                                                 ctypes.POINTER(OptimOptions), _vp, _vp, _vp]),
     "srhip_optimize_constants_starts": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64,
                                                        ctypes.POINTER(OptimOptions), _vp, _vp, _vp, _vp, _vp]),
+    "srhip_eval_loss_grad_expr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "srhip_optimize_constants_expr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(OptimOptions),
+                                                     _vp, _vp, _vp, _vp, _vp]),
     "srhip_eval_loss_grad_rowsets": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _vp, _vp, _vp, _vp]),
     "srhip_optimize_constants_rowsets": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _vp,
                                                         ctypes.POINTER(OptimOptions), _vp, _vp, _vp, _vp, _vp, _vp]),

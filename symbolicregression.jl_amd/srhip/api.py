@@ -23,7 +23,7 @@ import numpy as np
 from .dataset import Dataset
 from .device import Program, get_context
 from .loss_expr import ExprLoss
-from .losses import is_device_loss
+from .losses import has_device_gradient, is_device_loss
 from .node import Node, count_nodes, flatten
 
 
@@ -418,6 +418,11 @@ def eval_grad_loss_batch(trees, dataset: Dataset, options, idx=None, idxs=None):
         idxs = list(idxs)
         if len(idxs) != len(trees):
             raise ValueError(f"{len(idxs)} row subsets for {len(trees)} trees")
+    if idxs is not None and not is_device_loss(options.elementwise_loss):
+        # no row-set form under a loss expression: one single-idx call per tree
+        parts = [eval_grad_loss_batch([t], dataset, options, idx=np.asarray(i)) for t, i in zip(trees, idxs)]
+        return (np.array([p[0][0] for p in parts], dtype=np.float64), [p[1][0] for p in parts],
+                np.array([p[2][0] for p in parts], dtype=bool))
     prog = compile_trees(trees, options, dataset.X.dtype)
     try:
         if idxs is not None:
@@ -442,6 +447,9 @@ def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None, i
     generator is consumed as a loop over the members would: first every member's ``batch_sample``, in
     member order, then one seed per member, in member order -- and each member's outcome has the bits
     of that loop.  ``idxs`` gives one row subset per member instead of the draws (no ``batch_sample``).
+    A loss given as an expression (``ExprLoss``): the same device optimiser under the expression's own exact
+    gradient (srhip_optimize_constants_expr); there is no row-set form for it, so in batching mode a member
+    list takes one single-``idx`` device call per member.
     A user ``loss_function`` (or a Python elementwise loss): host Newton / BFGS with finite
     differences over ``eval_loss`` (srhip.host_optim), whose evaluations run on the device."""
     from .node import get_constants, set_constants
@@ -483,7 +491,7 @@ def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None, i
     for members_idx, gidx in groups:
         if rowset_results is not None:
             results = [rowset_results[i] for i in members_idx]
-        elif options.loss_function is not None or not is_device_loss(options.elementwise_loss):
+        elif options.loss_function is not None or not has_device_gradient(options.elementwise_loss):
             results = _optimize_constants_host(dataset, [trees[i] for i in members_idx], options, rng, gidx)
         else:
             seed = int(rng.integers(0, 2**63 - 1))
@@ -503,7 +511,7 @@ def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None, i
             set_constants(trees[i], c)
             m = mlist[i]
             if hasattr(m, "tree"):
-                if options.loss_function is not None or not is_device_loss(options.elementwise_loss):
+                if options.loss_function is not None or not has_device_gradient(options.elementwise_loss):
                     lo = eval_loss(trees[i], dataset, options, regularization=True, idx=gidx)
                 elif dataset.has_units():
                     lo = lo + dimensional_regularization(trees[i], dataset, options)

@@ -259,13 +259,21 @@ class Program:
         return np.split(c, np.cumsum(nconst)[:-1])
 
     def eval_loss_grad(self, ds: DeviceDataset, loss, idx=None):
-        """(loss[T], grads: list of per-tree arrays (get_constants order), ok[T])."""
+        """(loss[T], grads: list of per-tree arrays (get_constants order), ok[T]).  An ExprLoss goes to
+        srhip_eval_loss_grad_expr (the expression's own exact derivative on the device)."""
+        from .loss_expr import ExprLoss
+
         nconst = self.num_constants()
         out = np.empty(self.ntrees, dtype=np.float64)
         grad = np.empty(int(nconst.sum()), dtype=np.float64)
         ok = np.empty(self.ntrees, dtype=np.uint8)
-        ls = loss.c_struct()
         idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        if isinstance(loss, ExprLoss):
+            check(_lib.load().srhip_eval_loss_grad_expr(self.ctx.handle, ds.handle, self.handle, loss.handle(self.dtype),
+                                                        ptr(idxa), 0 if idxa is None else len(idxa), ptr(out), ptr(grad),
+                                                        ptr(ok)))
+            return out, np.split(grad, np.cumsum(nconst)[:-1]), ok.astype(bool)
+        ls = loss.c_struct()
         check(_lib.load().srhip_eval_loss_grad(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls), ptr(idxa),
                                                0 if idxa is None else len(idxa), ptr(out), ptr(grad), ptr(ok)))
         splits = np.cumsum(nconst)[:-1]
@@ -295,19 +303,27 @@ class Program:
 
         starts: optional [nrestarts, sum nconst] restart points (get_constants order, tree-major)
         used instead of the library's draws.  Returns (loss[T] of the returned trees, improved[T],
-        fcalls[T]), plus the restart points used ([nrestarts, sum nconst]) if return_starts."""
+        fcalls[T]), plus the restart points used ([nrestarts, sum nconst]) if return_starts.
+        An ExprLoss goes to srhip_optimize_constants_expr."""
+        from .loss_expr import ExprLoss
+
         opt = _lib.OptimOptions(int(iterations), int(nrestarts), int(seed) & (2**64 - 1), float(g_tol))
         out = np.empty(self.ntrees, dtype=np.float64)
         imp = np.empty(self.ntrees, dtype=np.uint8)
         fc = np.empty(self.ntrees, dtype=np.int64)
-        ls = loss.c_struct()
+        expr = isinstance(loss, ExprLoss)
+        ls = None if expr else loss.c_struct()
         idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
         nall = int(self.num_constants().sum())
         sin = None
         if starts is not None:
             sin = np.ascontiguousarray(starts, dtype=np.float64).reshape(int(nrestarts), nall)
         sout = np.empty((int(nrestarts), nall), dtype=np.float64) if return_starts else None
-        if sin is None and sout is None:  # the library's own draws, not reported: the plain entry point
+        if expr:
+            check(_lib.load().srhip_optimize_constants_expr(
+                self.ctx.handle, ds.handle, self.handle, loss.handle(self.dtype), ptr(idxa),
+                0 if idxa is None else len(idxa), ctypes.byref(opt), ptr(sin), ptr(sout), ptr(out), ptr(imp), ptr(fc)))
+        elif sin is None and sout is None:  # the library's own draws, not reported: the plain entry point
             check(_lib.load().srhip_optimize_constants(
                 self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls), ptr(idxa), 0 if idxa is None else len(idxa),
                 ctypes.byref(opt), ptr(out), ptr(imp), ptr(fc)))

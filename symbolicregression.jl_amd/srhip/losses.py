@@ -250,3 +250,11 @@ def by_name(name: str) -> SupervisedLoss:
 
 def is_device_loss(loss) -> bool:
     return isinstance(loss, SupervisedLoss)
+
+
+def has_device_gradient(loss) -> bool:
+    """The device has the loss's exact gradient, and so its constant optimiser: a built-in loss
+    (srhip_optimize_constants*) or a loss given as an expression (srhip_optimize_constants_expr)."""
+    from .loss_expr import ExprLoss
+
+    return is_device_loss(loss) or isinstance(loss, ExprLoss)
