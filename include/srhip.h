@@ -456,6 +456,45 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
                                      const double* starts_in /*nullable*/, double* starts_out /*nullable*/,
                                      double* out_loss, uint8_t* out_improved, int64_t* out_fcalls);
 
+/* ---- loss expressions with one row subset per tree (batching mode under a custom elementwise_loss) ----
+ * row_offsets / rows, their validation (SRHIP_ERR_INVALID naming tree and position) and the meaning of
+ * "alone, in a one-tree program, with idx = its set" are those of srhip_eval_loss_rowsets; the expression's
+ * argument errors are srhip_eval_loss_expr's (nargs against the weighted / unweighted dataset, dtype,
+ * SRHIP_ERR_UNSUPPORTED for an Int32 program).  Two kinds of tree are settled inside the call by the one-tree
+ * single-idx expression call itself: a set longer than the entry point's cap, and (scoring) a tree whose
+ * record leaves the did_succeed decision open (near overflow).  srhip_rowsets_fallback_trees counts them.
+ *
+ * srhip_eval_loss_expr_rowsets: out_loss[t] / out_ok[t] are exactly (same bits) srhip_eval_loss_expr's.  One
+ * launch and one synchronisation: each wavefront stages its tree's rows by index, runs the interpreter in its
+ * prediction mode, then the loss program over its predictions, summing in the loss pass's order (blocks of
+ * srhip_lossx_block_rows() rows).  Cap: srhip_eval_loss_rowsets' (40 KB of the set's feature, y and w
+ * columns in whole tiles -- the predictions live in device scratch: 5120 rows for Float32 data with one
+ * feature, 1024 with 8 features and weights). */
+int srhip_eval_loss_expr_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog,
+                                 const srhip_loss_expr* e, const int64_t* row_offsets /*[ntrees+1]*/,
+                                 const int64_t* rows, double* out_loss, uint8_t* out_ok);
+/* out_loss[t], tree t's slice of out_grad and out_ok[t] are exactly (same bits) srhip_eval_loss_grad_expr's.
+ * The launch is srhip_eval_loss_grad_rowsets' (packed sets, one wavefront per (tree, constant chunk), 256-row
+ * blocks) with the expression's dual program as its loss stage.  Cap: srhip_eval_loss_grad_rowsets' (whole
+ * 256-row blocks under the same 40 KB: 1536 rows for Float32 data with 5 features, 768 for Float64). */
+int srhip_eval_loss_grad_expr_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* prog,
+                                      const srhip_loss_expr* e, const int64_t* row_offsets /*[ntrees+1]*/,
+                                      const int64_t* rows, double* out_loss, double* out_grad,
+                                      uint8_t* out_ok);
+/* For every tree, out_loss[t], out_improved[t], out_fcalls[t], the constants left in prog and its slice of
+ * starts_out are exactly (same bits) what srhip_optimize_constants_expr returns for tree t alone, with idx =
+ * its set and opt->seed = tree_seeds[t] (NULL: opt->seed + t).  Baseline and final re-score are one
+ * srhip_eval_loss_expr_rowsets launch each; an objective value that is not finite counts as +Inf
+ * (srhip_optimize_constants_expr's rule); restart draws, starts_in / starts_out, acceptance and out_fcalls as
+ * srhip_optimize_constants_rowsets.  Cap: srhip_eval_loss_grad_expr_rowsets' (a longer set: the single-idx
+ * optimiser on that tree, inside the call).  A failed call leaves prog's constants unchanged. */
+int srhip_optimize_constants_expr_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* prog,
+                                          const srhip_loss_expr* e, const int64_t* row_offsets /*[ntrees+1]*/,
+                                          const int64_t* rows, const srhip_optim_options* opt,
+                                          const uint64_t* tree_seeds /*[ntrees], nullable*/,
+                                          const double* starts_in /*nullable*/, double* starts_out /*nullable*/,
+                                          double* out_loss, uint8_t* out_improved, int64_t* out_fcalls);
+
 /* ---- measurement hooks (bench / profiling) --------------------------------------------- */
 /* Device time (ms) of the last main kernel on this context -- the interpreter of srhip_eval_loss /
  * srhip_eval_predict, or the dual-number kernel of srhip_eval_loss_grad -- measured with HIP events
@@ -472,6 +511,11 @@ int srhip_last_work(const srhip_ctx* ctx, int64_t out[4]);
  * launch of the wide Float32 loss kernel with its per-slot records); < 0 for a null context.  The
  * tests' way to see which form evaluated a population. */
 int64_t srhip_hot_form_launches(const srhip_ctx* ctx);
+/* Trees of the last row-set call on this context (srhip_eval_loss*_rowsets, srhip_eval_loss_grad*_rowsets,
+ * srhip_optimize_constants*_rowsets) that were settled by the one-tree single-idx call instead of the
+ * row-set kernel: sets over the cap and, when scoring, undecided trees; < 0 for a null context.  The tests'
+ * way to tell the kernel from the fallback. */
+int64_t srhip_rowsets_fallback_trees(const srhip_ctx* ctx);
 /* Per-program work counters: sum over trees of count_nodes / operator nodes. */
 int srhip_program_stats(const srhip_program* prog, int64_t* total_nodes, int64_t* total_opnodes,
                         int32_t* max_stack);

@@ -28,4 +28,16 @@ static_assert(sizeof(GradLossxArgs) <= 4096, "kernel arguments are limited to 4 
 hipError_t launch_grad_lossx(int dtype, int K, int kt, const GradArgs& a, const LossxProgram& lx, dim3 grid,
                              hipStream_t s);
 
+// grad_rowsets_kernel's arguments as they are, and the loss program beside them (srhip_grad_rowsets_lossx.hip)
+struct GradRowsetLossxArgs {
+  GradRowsetArgs g;
+  LossxProgram lx;
+};
+static_assert(sizeof(GradRowsetLossxArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+// launch_grad_rowsets with the loss stage running lx (a.loss_kind / loss_p0 are not read; a.weighted only
+// says whether the packed sets carry a weight column): the same chunks, packed sets and final records
+hipError_t launch_grad_rowsets_lossx(int dtype, int kt, const GradRowsetArgs& a, const LossxProgram& lx, int max_ld,
+                                     hipStream_t s);
+
 }  // namespace srhip

@@ -1,6 +1,7 @@
 // srhip_grad_tile.inc — the dual-number interpreter's tile body, included as text (not called) by grad_kernel
-// (srhip_grad.hip) and grad_rowsets_kernel (srhip_grad_rowsets.hip), so both run the same arithmetic in the same
-// order and neither kernel's code generation depends on the other.  SRHIP_GRAD_PART selects the section:
+// (srhip_grad.hip), grad_rowsets_kernel (srhip_grad_rowsets.hip) and the two kernels with a loss expression's
+// stage in place of part 2 (srhip_grad_lossx.hip, srhip_grad_rowsets_lossx.hip), so all run the same arithmetic
+// in the same order and no kernel's code generation depends on another.  SRHIP_GRAD_PART selects the section:
 //   1  one tile of one chunk: the bytecode loop over A[R] / S[K][R] (values, tangents, check fold M)
 //   2  the tile's rows folded into lacc / gacc[] in ascending row order (rows >= nrel masked)
 //   3  the six xor levels that turn the lanes' sums into the (chunk, row block) record

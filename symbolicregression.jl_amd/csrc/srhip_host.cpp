@@ -1585,14 +1585,27 @@ static int rowset_single(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pr
   return rc;
 }
 
-int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
-                            const int64_t* row_offsets, const int64_t* rows, double* out_loss, uint8_t* out_ok) {
-  if (!row_offsets || !rows || !out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
-  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+// The same tree under a loss expression: srhip_eval_loss_expr on the one-tree program
+static int rowset_single_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int32_t t,
+                              const srhip_loss_expr* e, const int64_t* rows, int64_t m, double* out_loss, uint8_t* out_ok) {
+  srhip_program* Q = nullptr;
+  int rc = subprogram(ctx, P, {t}, &Q);
   if (rc) return rc;
+  rc = srhip_eval_loss_expr(ctx, ds, Q, e, rows, m, out_loss, out_ok);
+  srhip_program_destroy(Q);
+  return rc;
+}
+
+// srhip_eval_loss_rowsets (loss) and srhip_eval_loss_expr_rowsets (e) after their argument checks: exactly one
+// of loss / e is set.  Under an expression the launch is rowsets_lossx_kernel (the interpreter in its prediction
+// mode, then the loss program in the same wave) and the weighted mean divides by the weight sum taken in
+// lossx_kernel's order; staging, statistics, records and decisions are one code path.
+static int eval_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
+                        const srhip_loss_expr* e, const int64_t* row_offsets, const int64_t* rows, double* out_loss,
+                        uint8_t* out_ok) {
+  int rc;
   const int32_t nt = P->ntrees;
-  rc = check_rowsets(ds, nt, row_offsets, rows);
-  if (rc) return rc;
+  ctx->rowsets_fallback = 0;
   if (nt == 0) return SRHIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   const int dtype = P->dtype;
@@ -1602,7 +1615,7 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
   if (dtype == SRHIP_F32 && (P->sbound.size() != 4 * (size_t)nt))
     return fail(SRHIP_ERR_INVALID, "Float32 program without its +/- bounds");
   // the sets a wave can stage go into the launch, longest and costliest first; the others run alone
-  const int cap = rowset_cap(dtype, nf, weighted), tile = 64 * rows_per_lane(dtype);
+  const int cap = e ? rowset_lossx_cap(dtype, nf, weighted) : rowset_cap(dtype, nf, weighted), tile = 64 * rows_per_lane(dtype);
   std::vector<int32_t> live, alone;
   int64_t longest = 0;
   for (int32_t t = 0; t < nt; ++t) {
@@ -1621,7 +1634,7 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
   const int nl = (int)live.size();
   ResultSet* const rs = &ctx->rs[0];
   const FeatStat* fstat = nullptr;
-  const double* wsum = nullptr;
+  const double* wsum = nullptr;  // the mean's denominator of a weighted dataset
   static thread_local std::vector<uint64_t> r_loss, r_chk, r_rows, r_fs;
   if (nl > 0) {
     const int ld_lds = (int)((longest + tile - 1) / tile * tile);
@@ -1649,7 +1662,10 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
     HIP_TRY(rs->h_chk.ensure((size_t)nt * 8, hipHostMallocCoherent));
     HIP_TRY(rs->h_rows.ensure((size_t)(nt + 1) * 8, hipHostMallocCoherent));
     const size_t fs_bytes = (size_t)nt * std::max<int64_t>(1, nf) * sizeof(FeatStat);
-    HIP_TRY(ctx->h_rowsets.ensure(fs_bytes + (size_t)nt * sizeof(double), hipHostMallocCoherent));
+    // [feature statistics | position-order weight sums | (expression) weight sums in the loss pass's order]
+    const size_t rs_bytes = fs_bytes + (size_t)nt * sizeof(double) * (e ? 2 : 1);
+    HIP_TRY(ctx->h_rowsets.ensure(rs_bytes, hipHostMallocCoherent));
+    if (e) HIP_TRY(ctx->lossx_work.ensure((size_t)nl * ld_lds * dtype_size(dtype)));  // the waves' predictions
     RowsetArgs a{};
     a.e.code = P->code_dev;
     a.e.prog_off = P->off_dev;
@@ -1667,13 +1683,13 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
     a.e.nch = cpb;
     a.e.cpb = cpb;
     a.e.trees_per_group = 1;
-    a.e.loss_kind = loss->kind;
-    a.e.loss_p0 = loss->p0;
+    a.e.loss_kind = loss ? loss->kind : 0;
+    a.e.loss_p0 = loss ? loss->p0 : 0.0;
     a.e.weighted = weighted ? 1 : 0;
-    a.e.has_y = 1;
+    a.e.has_y = e ? 0 : 1;
     a.e.max_steps = P->max_len;
     a.e.fused = 1;
-    a.e.fused_loss = rs->h_loss.p;
+    a.e.fused_loss = e ? nullptr : rs->h_loss.p;
     a.e.fused_chk = dtype == SRHIP_I32 ? nullptr : rs->h_chk.p;
     a.e.fused_rows = (int64_t*)rs->h_rows.p;
     a.row_off = (const int64_t*)ctx->vidx.p;
@@ -1684,7 +1700,11 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
     a.fstat = (FeatStat*)ctx->h_rowsets.p;
     a.wsum = weighted ? (double*)((uint8_t*)ctx->h_rowsets.p + fs_bytes) : nullptr;
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(launch_rowsets(dtype, a, nl, ctx->stream));
+    if (e)
+      HIP_TRY(launch_rowsets_lossx(dtype, a, e->prog, ctx->lossx_work.p, (double*)rs->h_loss.p,
+                                   weighted ? (double*)((uint8_t*)ctx->h_rowsets.p + fs_bytes) + nt : nullptr, nl, ctx->stream));
+    else
+      HIP_TRY(launch_rowsets(dtype, a, nl, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     rc = stream_wait(ctx);  // the call's one synchronisation
     if (rc) return rc;
@@ -1692,13 +1712,13 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
     r_loss.resize(nt);
     r_chk.resize(nt);
     r_rows.resize(nt);
-    r_fs.resize((fs_bytes + (size_t)nt * sizeof(double)) / 8);
+    r_fs.resize(rs_bytes / 8);
     memcpy(r_loss.data(), rs->h_loss.p, (size_t)nt * 8);
     if (dtype != SRHIP_I32) memcpy(r_chk.data(), rs->h_chk.p, (size_t)nt * (dtype == SRHIP_F32 ? 4 : 8));
     memcpy(r_rows.data(), rs->h_rows.p, (size_t)nt * 8);
     memcpy(r_fs.data(), ctx->h_rowsets.p, r_fs.size() * 8);
     fstat = (const FeatStat*)r_fs.data();
-    wsum = weighted ? (const double*)((const uint8_t*)r_fs.data() + fs_bytes) : nullptr;
+    wsum = weighted ? (const double*)((const uint8_t*)r_fs.data() + fs_bytes) + (e ? nt : 0) : nullptr;
   }
   // every launched tree decided on its own record: its set's rows, feature statistics and +/- bound
   int64_t work[4] = {0, 0, 0, 0};
@@ -1734,7 +1754,10 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
   }
   alone.insert(alone.end(), undecided.begin(), undecided.end());
   for (int32_t t : alone) {
-    rc = rowset_single(ctx, ds, P, t, loss, rows + row_offsets[t], row_offsets[t + 1] - row_offsets[t], out_loss + t, out_ok + t);
+    const int64_t* const set = rows + row_offsets[t];
+    const int64_t m = row_offsets[t + 1] - row_offsets[t];
+    rc = e ? rowset_single_expr(ctx, ds, P, t, e, set, m, out_loss + t, out_ok + t)
+           : rowset_single(ctx, ds, P, t, loss, set, m, out_loss + t, out_ok + t);
     if (rc) return rc;
     if (std::find(undecided.begin(), undecided.end(), t) == undecided.end())
       for (int i = 0; i < 4; ++i) work[i] += ctx->work[i];
@@ -1745,8 +1768,32 @@ int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
     ctx->last_ev1 = ctx->ev1;
     ctx->timed = true;
   }
+  ctx->rowsets_fallback = (int64_t)alone.size();
   return SRHIP_OK;
 }
+
+int srhip_eval_loss_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
+                            const int64_t* row_offsets, const int64_t* rows, double* out_loss, uint8_t* out_ok) {
+  if (!row_offsets || !rows || !out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
+  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  rc = check_rowsets(ds, P->ntrees, row_offsets, rows);
+  if (rc) return rc;
+  return eval_rowsets(ctx, ds, P, loss, nullptr, row_offsets, rows, out_loss, out_ok);
+}
+
+int srhip_eval_loss_expr_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss_expr* e,
+                                 const int64_t* row_offsets, const int64_t* rows, double* out_loss, uint8_t* out_ok) {
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  if (!row_offsets || !rows || !out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
+  int rc = check_loss_expr_args(ctx, ds, P, e);
+  if (rc) return rc;
+  rc = check_rowsets(ds, P->ntrees, row_offsets, rows);
+  if (rc) return rc;
+  return eval_rowsets(ctx, ds, P, nullptr, e, row_offsets, rows, out_loss, out_ok);
+}
+
+int64_t srhip_rowsets_fallback_trees(const srhip_ctx* ctx) { return ctx ? ctx->rowsets_fallback : -1; }
 
 // srhip_eval_loss_submit / _wait: an evaluation whose launches return at once (queued on the context's
 // stream behind whatever is in flight there) and whose records, decisions and outputs are taken at wait.

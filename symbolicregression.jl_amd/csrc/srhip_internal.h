@@ -228,6 +228,7 @@ struct srhip_ctx {
   // evaluated node-rows, nominal node-rows (every live tree on every row), evaluated operator-node
   // rows, evaluated tree-rows
   int64_t work[4] = {0, 0, 0, 0};
+  int64_t rowsets_fallback = 0;  // trees of the last row-set call settled by the one-tree single-idx call
   int64_t hot_launches = 0;  // hot-form launches so far (srhip_hot_form_launches)
   // a second context on the same device (own stream and buffers), created on first use by the
   // constant optimiser, which runs half of the population on it from a second host thread

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "srhip_isa.h"
+#include "srhip_lossx.h"
 #include "srhip_tail_shares.h"
 
 namespace srhip {
@@ -203,5 +204,21 @@ struct RowsetArgs {
 constexpr int ROWSET_LDS_BUDGET = 40 * 1024;
 int rowset_cap(int dtype, int64_t nfeat, bool weighted);
 hipError_t launch_rowsets(int dtype, const RowsetArgs& a, int nlaunch, hipStream_t s);
+
+// The same under a loss given as an expression (srhip_rowsets_lossx.hip; srhip_eval_loss_expr_rowsets).  r.e is
+// a fused single-row-block MODE_PRED launch of one-tree groups (no y / w / loss kind: the kernel stages y and w
+// itself; fused_chk and fused_rows as above, fused_loss unused); the loss program travels beside it.
+struct RowsetLossxArgs {
+  RowsetArgs r;
+  LossxProgram lx;
+  void* pred;        // [launched trees][ld_lds] T: each wave's predictions (device scratch)
+  double* out_loss;  // [program trees] each set's loss sum in lossx_kernel's order (coherent host)
+  double* out_wsum;  // [program trees] each set's weight sum in the same order (coherent host), or nullptr
+};
+static_assert(sizeof(RowsetLossxArgs) <= 4096, "kernel arguments are limited to 4 KB");
+// the longest set a wave stages under an expression loss: rowset_cap (Float32 / Float64; 0 otherwise)
+int rowset_lossx_cap(int dtype, int64_t nfeat, bool weighted);
+hipError_t launch_rowsets_lossx(int dtype, const RowsetArgs& a, const LossxProgram& lx, void* pred, double* out_loss,
+                                double* out_wsum, int nlaunch, hipStream_t s);
 
 }  // namespace srhip

@@ -373,12 +373,14 @@ struct RowsetBackend {
     a.nchunks = nch;
     a.nfeat = (int32_t)ds->nfeat;
     a.gd_nd = 0;
-    a.loss_kind = loss.kind->kind;  // (built-in kinds only: eval_grad_items)
-    a.loss_p0 = loss.kind->p0;
+    a.loss_kind = loss.kind ? loss.kind->kind : 0;  // (an expression: its program travels beside these arguments)
+    a.loss_p0 = loss.kind ? loss.kind->p0 : 0.0;
     a.weighted = ds->weighted ? 1 : 0;
     a.max_steps = P->gmax_len;
     if (ev0) HIP_TRY(hipEventRecord(ev0, ctx->stream));
-    HIP_TRY(launch_grad_rowsets(P->dtype, ps.kt, a, max_ld[pi], ctx->stream));
+    // the kernel by the loss selector, as ViewBackend: grad_rowsets_kernel, or grad_rowsets_lossx_kernel
+    if (loss.expr) HIP_TRY(launch_grad_rowsets_lossx(P->dtype, ps.kt, a, *loss.expr, max_ld[pi], ctx->stream));
+    else HIP_TRY(launch_grad_rowsets(P->dtype, ps.kt, a, max_ld[pi], ctx->stream));
     return SRHIP_OK;
   }
 
@@ -501,7 +503,6 @@ static int eval_grad_items_on(srhip_ctx* ctx, srhip_program* P, Backend& be, con
 static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss,
                            const View& v, const std::vector<GradItem>& items, bool timed, const RowsetBatch* rb) {
   if (rb) {
-    if (!loss.kind) return fail(SRHIP_ERR_UNSUPPORTED, "row sets under a loss expression");
     RowsetBackend be{ctx, ds, P, loss, *rb};
     return eval_grad_items_on(ctx, P, be, items, timed);
   }
@@ -1540,13 +1541,26 @@ namespace {
 // gathered once into the context's packed buffer.  Sets over the cap, statically failing trees (the
 // evaluation took no statistics of their sets) and a non-default SRHIP_GRAD_RB stay unstaged: the
 // single-idx path.
-int make_rowset_batch(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+// The loss of a row-set call: a built-in kind or an expression (exactly one is set)
+struct RowsetLoss {
+  const srhip_loss* kind = nullptr;
+  const srhip_loss_expr* expr = nullptr;
+  LossSel sel() const { return expr ? LossSel(&expr->prog) : LossSel(kind); }
+  // the call's evaluator: one rowsets launch
+  int score(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const int64_t* row_offsets,
+            const int64_t* rows, double* out_loss, uint8_t* out_ok) const {
+    return expr ? srhip_eval_loss_expr_rowsets(ctx, ds, P, expr, row_offsets, rows, out_loss, out_ok)
+                : srhip_eval_loss_rowsets(ctx, ds, P, kind, row_offsets, rows, out_loss, out_ok);
+  }
+};
+
+int make_rowset_batch(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const RowsetLoss& loss,
                       const int64_t* row_offsets, const int64_t* rows, RowsetBatch& rb, double* base_loss,
                       uint8_t* base_ok) {
   const int32_t nt = P->ntrees;
   const int64_t nf = ds->nfeat;
   const bool weighted = ds->weighted;
-  int rc = srhip_eval_loss_rowsets(ctx, ds, P, loss, row_offsets, rows, base_loss, base_ok);
+  int rc = loss.score(ctx, ds, P, row_offsets, rows, base_loss, base_ok);
   if (rc) return rc;
   rb.row_off = row_offsets;
   rb.rows = rows;
@@ -1600,20 +1614,13 @@ int make_rowset_batch(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P,
   return SRHIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int srhip_eval_loss_grad_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
-                                 const int64_t* row_offsets, const int64_t* rows, double* out_loss, double* out_grad,
-                                 uint8_t* out_ok) {
-  if (!row_offsets || !rows || !out_loss || !out_grad || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
-  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
-  if (rc) return rc;
-  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant gradients need Float32 / Float64");
+// srhip_eval_loss_grad_rowsets / srhip_eval_loss_grad_expr_rowsets after their argument checks
+int grad_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const RowsetLoss& loss,
+                 const int64_t* row_offsets, const int64_t* rows, double* out_loss, double* out_grad, uint8_t* out_ok) {
   const int32_t nt = P->ntrees;
-  rc = check_rowsets(ds, nt, row_offsets, rows);
+  int rc = check_rowsets(ds, nt, row_offsets, rows);
   if (rc) return rc;
+  ctx->rowsets_fallback = 0;
   if (nt == 0) return SRHIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   RowsetBatch rb;
@@ -1624,35 +1631,54 @@ int srhip_eval_loss_grad_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_
   const std::vector<int64_t> coff = const_offsets(*P);
   // the unstaged sets first, each through the single-idx call on a one-tree program
   std::vector<int32_t> staged;
+  int64_t nalone = 0;
   for (int32_t t = 0; t < nt; ++t) {
     if (rb.staged[t]) {
       staged.push_back(t);
       continue;
     }
+    if (loss.expr && P->info[t].static_fail) {
+      // srhip_eval_loss_grad_expr's answer for a tree that fails whatever the rows: +Inf, a zero slice, not ok
+      out_loss[t] = INFINITY;
+      std::fill(out_grad + coff[t], out_grad + coff[t + 1], 0.0);
+      out_ok[t] = 0;
+      continue;
+    }
     srhip_program* Q = nullptr;
     rc = subprogram(ctx, P, {t}, &Q);
     if (rc) return rc;
-    rc = srhip_eval_loss_grad(ctx, ds, Q, loss, rows + row_offsets[t], row_offsets[t + 1] - row_offsets[t], out_loss + t,
-                              out_grad + coff[t], out_ok + t);
+    const int64_t* const set = rows + row_offsets[t];
+    const int64_t m = row_offsets[t + 1] - row_offsets[t];
+    rc = loss.expr ? srhip_eval_loss_grad_expr(ctx, ds, Q, loss.expr, set, m, out_loss + t, out_grad + coff[t], out_ok + t)
+                   : srhip_eval_loss_grad(ctx, ds, Q, loss.kind, set, m, out_loss + t, out_grad + coff[t], out_ok + t);
     srhip_program_destroy(Q);
     if (rc) return rc;
+    nalone += 1;
   }
+  ctx->rowsets_fallback = nalone;
   if (staged.empty()) return SRHIP_OK;
   P->g_want_derived = false;  // (off below 8192 rows in the single-idx path too)
   const View none{};
-  return eval_grad(ctx, ds, P, loss, none, staged, coff, out_loss, out_grad, out_ok, nullptr, 0, -1, nullptr, true, &rb);
+  rc = eval_grad(ctx, ds, P, loss.sel(), none, staged, coff, out_loss, out_grad, out_ok, nullptr, 0, -1, nullptr, true, &rb);
+  if (rc) return rc;
+  if (loss.expr)
+    for (int32_t t : staged)  // srhip_eval_loss_grad_expr: a failed tree is +Inf and a zero slice, whatever its rows summed to
+      if (!out_ok[t]) {
+        out_loss[t] = INFINITY;
+        std::fill(out_grad + coff[t], out_grad + coff[t + 1], 0.0);
+      }
+  return SRHIP_OK;
 }
 
-int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
-                                     const int64_t* row_offsets, const int64_t* rows, const srhip_optim_options* opt,
-                                     const uint64_t* tree_seeds, const double* starts_in, double* starts_out,
-                                     double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
-  if (!row_offsets || !rows || !opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
-  int rc = check_optim_args(ctx, ds, P, loss, opt);
-  if (rc) return rc;
+// srhip_optimize_constants_rowsets / srhip_optimize_constants_expr_rowsets after their argument checks
+int optimize_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const RowsetLoss& loss,
+                     const int64_t* row_offsets, const int64_t* rows, const srhip_optim_options* opt,
+                     const uint64_t* tree_seeds, const double* starts_in, double* starts_out, double* out_loss,
+                     uint8_t* out_improved, int64_t* out_fcalls) {
   const int32_t nt = P->ntrees;
-  rc = check_rowsets(ds, nt, row_offsets, rows);
+  int rc = check_rowsets(ds, nt, row_offsets, rows);
   if (rc) return rc;
+  ctx->rowsets_fallback = 0;
   if (nt == 0) return SRHIP_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   // baseline = f(tree) with the evaluator itself (src/ConstantOptimization.jl:49), every tree on its own set
@@ -1690,7 +1716,7 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
     const View none{};
     const double tb = now_s();
     reset_optim_counters(false, false);
-    rc = bfgs_pipelined(ctx, ds, P, loss, none, trees, coff, opt->iterations, g_tol, starts, best_x, best_f, fcalls, &rb);
+    rc = bfgs_pipelined(ctx, ds, P, loss.sel(), none, trees, coff, opt->iterations, g_tol, starts, best_x, best_f, fcalls, &rb);
     const char* te = getenv("SRHIP_OPTIM_TIMING");  // the single-idx entry point's line, for this path
     if (te && *te && *te != '0')
       fprintf(stderr,
@@ -1720,8 +1746,11 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
       double l1 = 0.0;
       uint8_t imp = 0;
       int64_t fc = 0;
-      rc = srhip_optimize_constants_starts(ctx, ds, Q, loss, rows + row_offsets[t], row_offsets[t + 1] - row_offsets[t], &o1,
-                                           opt->nrestarts > 0 ? sin.data() : nullptr, nullptr, &l1, &imp, &fc);
+      const int64_t* const set = rows + row_offsets[t];
+      const int64_t m = row_offsets[t + 1] - row_offsets[t];
+      const double* const sp = opt->nrestarts > 0 ? sin.data() : nullptr;
+      rc = loss.expr ? srhip_optimize_constants_expr(ctx, ds, Q, loss.expr, set, m, &o1, sp, nullptr, &l1, &imp, &fc)
+                     : srhip_optimize_constants_starts(ctx, ds, Q, loss.kind, set, m, &o1, sp, nullptr, &l1, &imp, &fc);
       if (rc == SRHIP_OK) {
         double* cst = final_x.data() + coff[t];
         get_consts(Q->nodes.data(), 0, cst);
@@ -1740,10 +1769,67 @@ int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, sr
   if (rc) return rc;
   // the loss of the returned trees, by the evaluator (the reference re-scores accepted members): one launch
   std::vector<uint8_t> ok(nt);
-  rc = srhip_eval_loss_rowsets(ctx, ds, P, loss, row_offsets, rows, out_loss, ok.data());
-  if (rc) return rc;
+  rc = loss.score(ctx, ds, P, row_offsets, rows, out_loss, ok.data());
+  if (rc) {
+    if (loss.expr) {  // a failed call leaves the constants as they came
+      const std::string msg = last_error();
+      restore_constants(*P, x0);
+      return fail(rc, "%s", msg.c_str());
+    }
+    return rc;
+  }
+  ctx->rowsets_fallback = (int64_t)alone.size();
   report_fcalls(fcalls, out_improved, out_fcalls);
   return SRHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srhip_eval_loss_grad_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                                 const int64_t* row_offsets, const int64_t* rows, double* out_loss, double* out_grad,
+                                 uint8_t* out_ok) {
+  if (!row_offsets || !rows || !out_loss || !out_grad || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
+  const int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant gradients need Float32 / Float64");
+  return grad_rowsets(ctx, ds, P, RowsetLoss{loss, nullptr}, row_offsets, rows, out_loss, out_grad, out_ok);
+}
+
+int srhip_eval_loss_grad_expr_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss_expr* e,
+                                      const int64_t* row_offsets, const int64_t* rows, double* out_loss,
+                                      double* out_grad, uint8_t* out_ok) {
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  if (!row_offsets || !rows || !out_loss || !out_grad || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
+  const int rc = check_loss_expr_args(ctx, ds, P, e);
+  if (rc) return rc;
+  return grad_rowsets(ctx, ds, P, RowsetLoss{nullptr, e}, row_offsets, rows, out_loss, out_grad, out_ok);
+}
+
+int srhip_optimize_constants_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                                     const int64_t* row_offsets, const int64_t* rows, const srhip_optim_options* opt,
+                                     const uint64_t* tree_seeds, const double* starts_in, double* starts_out,
+                                     double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
+  if (!row_offsets || !rows || !opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
+  const int rc = check_optim_args(ctx, ds, P, loss, opt);
+  if (rc) return rc;
+  return optimize_rowsets(ctx, ds, P, RowsetLoss{loss, nullptr}, row_offsets, rows, opt, tree_seeds, starts_in, starts_out,
+                          out_loss, out_improved, out_fcalls);
+}
+
+int srhip_optimize_constants_expr_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P,
+                                          const srhip_loss_expr* e, const int64_t* row_offsets, const int64_t* rows,
+                                          const srhip_optim_options* opt, const uint64_t* tree_seeds,
+                                          const double* starts_in, double* starts_out, double* out_loss,
+                                          uint8_t* out_improved, int64_t* out_fcalls) {
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  if (!row_offsets || !rows || !opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
+  if (opt->iterations < 0 || opt->nrestarts < 0) return fail(SRHIP_ERR_INVALID, "negative iterations / restarts");
+  const int rc = check_loss_expr_args(ctx, ds, P, e);
+  if (rc) return rc;
+  return optimize_rowsets(ctx, ds, P, RowsetLoss{nullptr, e}, row_offsets, rows, opt, tree_seeds, starts_in, starts_out,
+                          out_loss, out_improved, out_fcalls);
 }
 
 }  // extern "C"

@@ -131,6 +131,11 @@ SIGNATURES = {
     "srhip_eval_loss_grad_rowsets": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _vp, _vp, _vp, _vp]),
     "srhip_optimize_constants_rowsets": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _vp,
                                                         ctypes.POINTER(OptimOptions), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srhip_eval_loss_expr_rowsets": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srhip_eval_loss_grad_expr_rowsets": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srhip_optimize_constants_expr_rowsets": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp,
+                                                             ctypes.POINTER(OptimOptions), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srhip_rowsets_fallback_trees": (_i64, [_vp]),
     "srhip_batcher_create": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(Operators), ctypes.POINTER(Loss), _i32, _i32,
                                             ctypes.POINTER(_vp)]),
     "srhip_batcher_set_clients": (ctypes.c_int, [_vp, _i32]),

@@ -23,7 +23,7 @@ import numpy as np
 from .dataset import Dataset
 from .device import Program, get_context
 from .loss_expr import ExprLoss
-from .losses import has_device_gradient, is_device_loss
+from .losses import has_device_gradient, has_device_rowsets, is_device_loss
 from .node import Node, count_nodes, flatten
 
 
@@ -140,13 +140,14 @@ def eval_loss_rowsets_batch(trees, dataset: Dataset, options, idxs, regularizati
     fresh minibatch per score, src/LossFunctions.jl:114-127), all trees in one device launch:
     (loss[ntrees] float64, ok[ntrees]), element t exactly eval_loss_batch([trees[t]], ..., idx=idxs[t]).
 
-    A user loss_function, or an elementwise loss the device does not implement, takes the per-tree
-    loop through eval_loss(..., idx=idxs[t])."""
+    A loss given as an expression (``ExprLoss``) is one launch too (srhip_eval_loss_expr_rowsets).  A user
+    loss_function, or an elementwise loss the device does not implement, takes the per-tree loop through
+    eval_loss(..., idx=idxs[t])."""
     trees = _as_trees(trees)
     idxs = list(idxs)
     if len(idxs) != len(trees):
         raise ValueError(f"{len(idxs)} row subsets for {len(trees)} trees")
-    if options.loss_function is not None or not is_device_loss(options.elementwise_loss):
+    if options.loss_function is not None or not has_device_rowsets(options.elementwise_loss):
         out = np.array([eval_loss(t, dataset, options, regularization=regularization, idx=i)
                         for t, i in zip(trees, idxs)], dtype=np.float64)
         return out, np.isfinite(out)
@@ -410,7 +411,8 @@ def eval_grad_loss_batch(trees, dataset: Dataset, options, idx=None, idxs=None):
     """Loss and its exact gradient w.r.t. each tree's constants (get_constants order), one launch:
     (loss[T], [grad per tree], ok[T]).  The loss-level counterpart of eval_grad_tree_array
     (src/InterfaceDynamicExpressions.jl:118-124, variable=false).  idxs: one row subset per tree
-    (like eval_loss_rowsets_batch) instead of the shared idx, still one launch."""
+    (like eval_loss_rowsets_batch) instead of the shared idx, still one launch -- for a built-in loss and for
+    a loss given as an expression (srhip_eval_loss_grad_expr_rowsets)."""
     trees = _as_trees(trees)
     if idxs is not None:
         if idx is not None:
@@ -418,8 +420,8 @@ def eval_grad_loss_batch(trees, dataset: Dataset, options, idx=None, idxs=None):
         idxs = list(idxs)
         if len(idxs) != len(trees):
             raise ValueError(f"{len(idxs)} row subsets for {len(trees)} trees")
-    if idxs is not None and not is_device_loss(options.elementwise_loss):
-        # no row-set form under a loss expression: one single-idx call per tree
+    if idxs is not None and not has_device_rowsets(options.elementwise_loss):
+        # no row-set form for this loss: one single-idx call per tree
         parts = [eval_grad_loss_batch([t], dataset, options, idx=np.asarray(i)) for t, i in zip(trees, idxs)]
         return (np.array([p[0][0] for p in parts], dtype=np.float64), [p[1][0] for p in parts],
                 np.array([p[2][0] for p in parts], dtype=bool))
@@ -448,8 +450,10 @@ def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None, i
     member order, then one seed per member, in member order -- and each member's outcome has the bits
     of that loop.  ``idxs`` gives one row subset per member instead of the draws (no ``batch_sample``).
     A loss given as an expression (``ExprLoss``): the same device optimiser under the expression's own exact
-    gradient (srhip_optimize_constants_expr); there is no row-set form for it, so in batching mode a member
-    list takes one single-``idx`` device call per member.
+    gradient (srhip_optimize_constants_expr).  With ``idxs`` a member list is one device call here too
+    (srhip_optimize_constants_expr_rowsets, each member's outcome the bits of the per-member loop).  The one
+    remaining step: where this function draws the minibatches itself (``options.batching``, no ``idxs``) a
+    member list under an ``ExprLoss`` still takes one single-``idx`` device call per member.
     A user ``loss_function`` (or a Python elementwise loss): host Newton / BFGS with finite
     differences over ``eval_loss`` (srhip.host_optim), whose evaluations run on the device."""
     from .node import get_constants, set_constants
@@ -476,7 +480,8 @@ def optimize_constants(dataset: Dataset, members, options, rng=None, idx=None, i
     num_evals = 0.0
     rowset_results = None
     if (per_member and not single and options.loss_function is None
-            and is_device_loss(options.elementwise_loss)):
+            and (is_device_loss(options.elementwise_loss)
+                 or (idxs is not None and isinstance(options.elementwise_loss, ExprLoss)))):
         # one subset per member of a list, device loss: one call for all of them
         seeds = [int(rng.integers(0, 2**63 - 1)) for _ in groups]
         prog = compile_trees(trees, options, dataset.X.dtype)

@@ -42,6 +42,11 @@ class Context:
         """Launches of the interpreter's hot form on this context so far (srhip_hot_form_launches)."""
         return int(self._lib.srhip_hot_form_launches(self.handle))
 
+    def rowsets_fallback_trees(self) -> int:
+        """Trees of the last row-set call on this context that took the one-tree single-idx path
+        (srhip_rowsets_fallback_trees)."""
+        return int(self._lib.srhip_rowsets_fallback_trees(self.handle))
+
     def close(self):
         if self.handle:
             self._lib.srhip_ctx_destroy(self.handle)
@@ -221,10 +226,17 @@ class Program:
     def eval_loss_rowsets(self, ds: DeviceDataset, loss, idxs):
         """srhip_eval_loss_rowsets: tree t on its own row subset idxs[t] (0-based int arrays, one per tree,
         duplicates allowed, lengths may differ), all in one launch; (loss[T], ok[T]) with the bits of
-        eval_loss(ds, loss, idx=idxs[t]) on tree t alone."""
+        eval_loss(ds, loss, idx=idxs[t]) on tree t alone.  An ExprLoss goes to srhip_eval_loss_expr_rowsets."""
+        from .loss_expr import ExprLoss
+
         offsets, rows = pack_rowsets(idxs, self.ntrees)
         out = np.empty(self.ntrees, dtype=np.float64)
         ok = np.empty(self.ntrees, dtype=np.uint8)
+        if isinstance(loss, ExprLoss):
+            check(_lib.load().srhip_eval_loss_expr_rowsets(self.ctx.handle, ds.handle, self.handle,
+                                                           loss.handle(self.dtype), ptr(offsets), ptr(rows), ptr(out),
+                                                           ptr(ok)))
+            return out, ok.astype(bool)
         ls = loss.c_struct()
         check(_lib.load().srhip_eval_loss_rowsets(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls),
                                                   ptr(offsets), ptr(rows), ptr(out), ptr(ok)))
@@ -338,12 +350,20 @@ class Program:
     def eval_loss_grad_rowsets(self, ds: DeviceDataset, loss, idxs):
         """srhip_eval_loss_grad_rowsets: tree t on its own row subset idxs[t] (as eval_loss_rowsets), all in
         one launch; (loss[T], grads: list of per-tree arrays, ok[T]) with the bits of
-        eval_loss_grad(ds, loss, idx=idxs[t]) on tree t alone."""
+        eval_loss_grad(ds, loss, idx=idxs[t]) on tree t alone.  An ExprLoss goes to
+        srhip_eval_loss_grad_expr_rowsets."""
+        from .loss_expr import ExprLoss
+
         offsets, rows = pack_rowsets(idxs, self.ntrees)
         nconst = self.num_constants()
         out = np.empty(self.ntrees, dtype=np.float64)
         grad = np.empty(int(nconst.sum()), dtype=np.float64)
         ok = np.empty(self.ntrees, dtype=np.uint8)
+        if isinstance(loss, ExprLoss):
+            check(_lib.load().srhip_eval_loss_grad_expr_rowsets(self.ctx.handle, ds.handle, self.handle,
+                                                                loss.handle(self.dtype), ptr(offsets), ptr(rows),
+                                                                ptr(out), ptr(grad), ptr(ok)))
+            return out, np.split(grad, np.cumsum(nconst)[:-1]), ok.astype(bool)
         ls = loss.c_struct()
         check(_lib.load().srhip_eval_loss_grad_rowsets(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls),
                                                        ptr(offsets), ptr(rows), ptr(out), ptr(grad), ptr(ok)))
@@ -357,13 +377,17 @@ class Program:
         seeds: optional [T] seed of each tree's own restart generator (default seed + t).  starts /
         return_starts as optimize_constants.  Every tree's outcome has the bits of
         optimize_constants(idx=idxs[t], seed=seeds[t]) on tree t alone.  Returns (loss[T], improved[T],
-        fcalls[T]), plus the restart points used if return_starts."""
+        fcalls[T]), plus the restart points used if return_starts.  An ExprLoss goes to
+        srhip_optimize_constants_expr_rowsets."""
+        from .loss_expr import ExprLoss
+
         offsets, rows = pack_rowsets(idxs, self.ntrees)
         opt = _lib.OptimOptions(int(iterations), int(nrestarts), int(seed) & (2**64 - 1), float(g_tol))
         out = np.empty(self.ntrees, dtype=np.float64)
         imp = np.empty(self.ntrees, dtype=np.uint8)
         fc = np.empty(self.ntrees, dtype=np.int64)
-        ls = loss.c_struct()
+        expr = isinstance(loss, ExprLoss)
+        ls = None if expr else loss.c_struct()
         sd = None
         if seeds is not None:
             sd = np.ascontiguousarray([int(s) & (2**64 - 1) for s in seeds], dtype=np.uint64)
@@ -374,9 +398,14 @@ class Program:
         if starts is not None:
             sin = np.ascontiguousarray(starts, dtype=np.float64).reshape(int(nrestarts), nall)
         sout = np.empty((int(nrestarts), nall), dtype=np.float64) if return_starts else None
-        check(_lib.load().srhip_optimize_constants_rowsets(
-            self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls), ptr(offsets), ptr(rows), ctypes.byref(opt),
-            ptr(sd), ptr(sin), ptr(sout), ptr(out), ptr(imp), ptr(fc)))
+        if expr:
+            check(_lib.load().srhip_optimize_constants_expr_rowsets(
+                self.ctx.handle, ds.handle, self.handle, loss.handle(self.dtype), ptr(offsets), ptr(rows),
+                ctypes.byref(opt), ptr(sd), ptr(sin), ptr(sout), ptr(out), ptr(imp), ptr(fc)))
+        else:
+            check(_lib.load().srhip_optimize_constants_rowsets(
+                self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls), ptr(offsets), ptr(rows), ctypes.byref(opt),
+                ptr(sd), ptr(sin), ptr(sout), ptr(out), ptr(imp), ptr(fc)))
         if return_starts:
             return out, imp.astype(bool), fc, sout
         return out, imp.astype(bool), fc

@@ -252,6 +252,14 @@ def is_device_loss(loss) -> bool:
     return isinstance(loss, SupervisedLoss)
 
 
+def has_device_rowsets(loss) -> bool:
+    """The device has the one-launch row-set forms for the loss (every tree on a row subset of its own):
+    a built-in loss (srhip_*_rowsets) or a loss given as an expression (srhip_*_expr_rowsets)."""
+    from .loss_expr import ExprLoss
+
+    return is_device_loss(loss) or isinstance(loss, ExprLoss)
+
+
 def has_device_gradient(loss) -> bool:
     """The device has the loss's exact gradient, and so its constant optimiser: a built-in loss
     (srhip_optimize_constants*) or a loss given as an expression (srhip_optimize_constants_expr)."""
