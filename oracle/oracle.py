@@ -93,6 +93,20 @@ def eval_loss(nodes, binops, unaops, X, y, w=None, kind=0, p0=0.0):
     return le.value, lr.value, bool(ok)
 
 
+def loss_rows(pred, y, kind=0, p0=0.0):
+    """The elementwise loss l(pred_i, y_i) of every row, in the dtype of pred (Float32 or Float64), with the
+    parameter rounded to it as eval_loss does."""
+    lib = load()
+    pred = np.ascontiguousarray(pred)
+    sfx = _SFX[pred.dtype]
+    y = np.ascontiguousarray(y, dtype=pred.dtype)
+    out = np.empty_like(pred)
+    fn = _setup(getattr(lib, f"oracle_loss_rows_{sfx}"), None,
+                [ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64])
+    fn(int(kind), float(p0), _p(pred), _p(y), _p(out), len(pred))
+    return out
+
+
 def eval_loss_batch(nodes, offsets, binops, unaops, X, y, w=None, kind=0, p0=0.0, nthreads=0):
     """Every tree, OpenMP over trees. Returns (loss_exact, loss_ref, ok, threads_used)."""
     lib = load()

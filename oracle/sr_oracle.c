@@ -355,6 +355,13 @@ void oracle_srm_f32(int which, const float* x, float* y, int64_t n) {
     }
   }
 }
+/* one row's elementwise loss in T, l(pred_i, y_i), for tests/test_loss_values_table.py */
+void oracle_loss_rows_f32(int kind, double p0, const float* pred, const float* y, float* out, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) out[i] = loss_f32(kind, pred[i], y[i], (float)p0); /* (T)p0, as eval_loss */
+}
+void oracle_loss_rows_f64(int kind, double p0, const double* pred, const double* y, double* out, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) out[i] = loss_f64(kind, pred[i], y[i], p0);
+}
 float oracle_un_f32(int op, float x) { return un_f32(op, x); }
 double oracle_bin_f64(int op, double a, double b) { return bin_f64(op, a, b); }
 double oracle_un_f64(int op, double x) { return un_f64(op, x); }

@@ -264,7 +264,7 @@ __global__ void gather_kernel(const T* __restrict__ X, const T* __restrict__ y, 
   const int64_t j = idx[pad ? m - 1 : i];
   for (int f = 0; f < nfeat; ++f) Xd[(int64_t)f * ld_dst + i] = X[(int64_t)f * ld_src + j];
   if (y) yd[i] = y[j];
-  if (w) wd[i] = pad ? T(0) : w[j];
+  if (w) wd[i] = pad ? pad_weight<T>() : w[j];
 }
 
 // Per-feature statistics over the first m rows, for DynamicExpressions' feature-array checks

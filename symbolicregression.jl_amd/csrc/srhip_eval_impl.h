@@ -996,8 +996,14 @@ __device__ __attribute__((always_inline)) inline void loss_tile(const EvalArgs& 
       lv = loss_rows_generic<T, R>(A, yv, p.loss_kind, p0);  // (A first: it stays in v0-v15)
     }
     if (p.weighted) {
-      // padded rows carry w = 0 and a replicated (finite when ok) prediction
-      UNR for (int r = 0; r < R; ++r) lacc[r / RPC] += (double)(wv[r] * lv[r]);
+      // a padded row (weight -0.0, srhip_kernels.h pad_weight) repeats the last row, whose loss may be
+      // Inf though its prediction is finite: it counts as 0 * 0, not 0 * Inf = NaN.  No branch and no
+      // row index here: either costs the wide Float32 kernel scalar registers it does not have.  A
+      // finite 0 * l was an exact zero too, so every finite sum keeps its bits.
+      UNR for (int r = 0; r < R; ++r) {
+        const T l = is_pad_weight(wv[r]) ? T(0) : lv[r];
+        lacc[r / RPC] += (double)(wv[r] * l);
+      }
     } else {
       if (!full) {
         UNR for (int r = 0; r < R; ++r) {

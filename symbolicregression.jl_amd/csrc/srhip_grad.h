@@ -71,7 +71,7 @@ hipError_t launch_grad_derive(int dtype, const void* X, void* Xd, int64_t ld, co
 // A chunk is (program slot, first constant c0, tree whose row set it reads).  The sets are packed once
 // per call by launch_grad_rowsets_pack: set t at element offset set_off[t], [nfeat + 1 (+ 1 weighted)]
 // columns (features, y, w) of ld_t = set_m[t] rounded up to GRAD_ROWSET_RB rows, the positions past the
-// set's end replicating its last row (weight 0) as a gathered view's padding does.
+// set's end replicating its last row (the padding weight -0.0) as a gathered view's padding does.
 constexpr int GRAD_ROWSET_RB = 256;  // the row block of grad_plan: a set's partial sums are per 256 rows
 struct GradRowsetArgs {
   const Ins* code;          // gradient programs of all slots

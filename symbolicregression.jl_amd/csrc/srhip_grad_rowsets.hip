@@ -114,7 +114,7 @@ __global__ __launch_bounds__(64) void grad_rowsets_kernel(GradRowsetArgs p) {
 }
 
 // The call's pack: workgroup t gathers set t by index, [column][ld_t], gather_kernel's padding rule
-// (positions past the set's end replicate its last row, with weight 0).  set_off[t] < 0: not packed
+// (positions past the set's end replicate its last row, with the padding weight -0.0).  set_off[t] < 0: not packed
 // (a set no wave can stage).
 template <typename T>
 __global__ __launch_bounds__(256) void grad_rowsets_pack_kernel(const T* __restrict__ X, const T* __restrict__ y,
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void grad_rowsets_pack_kernel(const T* __restr
     const int64_t j = rows[r0 + min(pos, m - 1)];  // in [0, n): checked on the host
     for (int f = 0; f < nfeat; ++f) dst[(int64_t)f * ld + pos] = X[(int64_t)f * src_ld + j];
     dst[(int64_t)nfeat * ld + pos] = y[j];
-    if (w) dst[(int64_t)(nfeat + 1) * ld + pos] = pos < m ? w[j] : T(0);
+    if (w) dst[(int64_t)(nfeat + 1) * ld + pos] = pos < m ? w[j] : pad_weight<T>();
   }
 }
 

@@ -1430,11 +1430,11 @@ int srhip_dataset_create(srhip_ctx* ctx, int dtype, const void* X, int64_t nfeat
     double s = 0.0;
     if (dtype == SRHIP_F64) {
       double* st = (double*)stage.p;
-      for (int64_t j = 0; j < d->ld; ++j) st[j] = j < n ? ((const double*)w)[j] : 0.0;
+      for (int64_t j = 0; j < d->ld; ++j) st[j] = j < n ? ((const double*)w)[j] + 0.0 : pad_weight<double>();  // (-0.0 + 0.0 = +0.0)
       for (int64_t j = 0; j < n; ++j) s += st[j];
     } else {
       float* st = (float*)stage.p;
-      for (int64_t j = 0; j < d->ld; ++j) st[j] = j < n ? ((const float*)w)[j] : 0.0f;
+      for (int64_t j = 0; j < d->ld; ++j) st[j] = j < n ? ((const float*)w)[j] + 0.0f : pad_weight<float>();
       for (int64_t j = 0; j < n; ++j) s += st[j];
     }
     d->sum_w = s;

@@ -38,6 +38,16 @@ constexpr int MODE_LOSS = 0, MODE_PRED = 1, MODE_PRECISE = 2;
 // Row blocks are whole chunks.
 constexpr int LOSS_CHUNK_4B = 1024, LOSS_CHUNK_8B = 256;
 inline int loss_chunk(int dtype) { return dtype == SRHIP_F64 ? LOSS_CHUNK_8B : LOSS_CHUNK_4B; }
+// The rows that pad a weighted dataset, a gathered view or a staged row set up to whole tiles repeat
+// the last row with the weight -0.0, the one weight no row of the caller has (an uploaded -0.0 is
+// stored as +0.0, which is the same weight in every product and sum).  The loss epilogue tells a
+// padded row by it (loss_tile): the repeated row's loss may be Inf at a finite prediction, and
+// 0 * Inf is NaN, where a caller's own zero weight must give what sum(w .* l) gives.
+template <typename T> __host__ __device__ inline T pad_weight() { return T(0); }  // (Int32: no weights)
+template <> __host__ __device__ inline float pad_weight<float>() { return -0.0f; }
+template <> __host__ __device__ inline double pad_weight<double>() { return -0.0; }
+__host__ __device__ inline bool is_pad_weight(float w) { return w == 0.0f && __builtin_signbit(w); }
+__host__ __device__ inline bool is_pad_weight(double w) { return w == 0.0 && __builtin_signbit(w); }
 
 struct FeatStat {
   double sum;           // f64 sum (Float64 data: sum of x * 2^-64)

@@ -6,7 +6,7 @@
 // CU takes the next tree as soon as one of its waves retires.  The wave
 //   1. stages its set's rows of every feature column, y and w BY INDEX from the resident dataset into
 //      its own LDS region [column][ld_lds] -- gather_kernel's rule: the positions past the set's end up
-//      to the end of its last tile replicate the set's last row, with weight 0;
+//      to the end of its last tile replicate the set's last row, with the padding weight -0.0;
 //   2. folds the set's per-feature statistics (f64 sum, non-finite count, max |x|) with the arithmetic
 //      of feature_stats_kernel / feature_stats_final for a single row chunk (256 strided partial sums,
 //      the same halving tree), and the weight sum in position order (gathered_weight_sum's loop);
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(64) void rowsets_kernel(RowsetArgs a) {
     const int64_t j = a.rows[r0 + min(p, m - 1)];  // in [0, n): checked on the host before the launch
     for (int c = 0; c < nx; ++c) lx[(int64_t)c * ld + p] = gX[(int64_t)c * a.src_ld + j];
     ly[p] = gy[j];
-    if (weighted) lw[p] = p < m ? gw[j] : T(0);
+    if (weighted) lw[p] = p < m ? gw[j] : pad_weight<T>();
   }
   __syncthreads();
 

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64) void rowsets_lossx_kernel(const RowsetLossxArgs
     const int64_t j = a.rows[r0 + min(p, m - 1)];  // in [0, n): checked on the host before the launch
     for (int c = 0; c < nx; ++c) lx[(int64_t)c * ld + p] = gX[(int64_t)c * a.src_ld + j];
     ly[p] = gy[j];
-    if (weighted) lw[p] = p < m ? gw[j] : T(0);
+    if (weighted) lw[p] = p < m ? gw[j] : pad_weight<T>();
   }
   __syncthreads();
 

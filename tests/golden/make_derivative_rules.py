@@ -21,9 +21,11 @@ reference value is evaluated at the exact stored input and rounded once to Float
   loss_d_D, loss_a_D [N]      residuals d = pred - y (distance losses), agreements a = y * pred (margin)
   loss_dl_D [20, N]           l'(d) or l'(a), the parameters being LOSS_P0 below
 
-N = 300 points per case: a 256-row block and a 44-row tail.  Function values are not stored: with them
-the file would pass its 256 KB limit, and no test needs them (predictions are compared bit for bit with
-the evaluator, which has its own parity tests).  Float arrays are stored as byte planes (load_table
+N = 300 points per case: a 256-row block and a 44-row tail.  Function values are not stored here: with
+them the file would pass its 256 KB limit.  Operator values have a table of their own (forward_values.npz;
+predictions are compared bit for bit with the evaluator), and so have the loss values l(d), l(a) at these
+very residuals and agreements: loss_values.npz (make_loss_values.py, which imports the loss names, parameters
+and kinks below and adds the points on and beside the kinks).  Float arrays are stored as byte planes (load_table
 below reads them back): the same bits, about a sixth smaller once deflated.
 
 Every input is a multiple of 2^-20 (Float32) / 2^-48 (Float64), so that the shifts and scalings the
