@@ -578,6 +578,30 @@ typedef struct srhip_plan_info {
   int64_t lds;            /* LDS bytes of a workgroup */
 } srhip_plan_info;
 int srhip_plan_eval(const srhip_plan_query* q, srhip_plan_info* out);
+/* The constant optimiser's state machine (srhip_optimize_constants: BFGS / one-constant Newton over
+ * BackTracking, best of the starts, value-only trials, speculative trial points) over a callback instead
+ * of the device, for tests.  No device is needed.  Every tree t with constants (const_offsets[t + 1] >
+ * const_offsets[t]) is optimised from starts[s][const_offsets[t] ..], s = 0 .. nstarts - 1; best_x
+ * ([sum nconst]), best_f and fcalls ([ntrees]) receive its best point, that point's objective and its
+ * objective calls; entries of trees without constants, and every output of a failed call, stay as they
+ * are.  *nlaunches (may be NULL): the callback calls made.  Each call evaluates nitems items: item i is
+ * tree tree[i] at the point x[x_off[i] ..] -- a tree's own next point, or a speculative one (at most
+ * spec_slots per call).  It writes f[i], finite or +Inf, and, unless value_only[i], the gradient at
+ * g[x_off[i] ..]; a non-zero result ends the run and is returned.  g_tol <= 0: 1e-8. */
+typedef int (*srhip_bfgs_eval_fn)(void* user, int32_t nitems, const int32_t* tree, const int64_t* x_off,
+                                  const double* x, const uint8_t* value_only, double* f, double* g);
+typedef struct srhip_bfgs_query {
+  int32_t ntrees, nstarts;
+  const int64_t* const_offsets; /* [ntrees + 1] */
+  const double* starts;         /* [nstarts][sum nconst] */
+  int32_t iterations;
+  int32_t value_trials;         /* trials after a line search's first are value-only */
+  int32_t spec_slots, spec_max_active, spec_max_depth; /* SRHIP_OPTIM_SPEC / _SPEC_ACTIVE / _SPEC_DEPTH */
+  int32_t pad;
+  double g_tol;
+} srhip_bfgs_query;
+int srhip_bfgs_host(const srhip_bfgs_query* q, srhip_bfgs_eval_fn eval, void* user, double* best_x, double* best_f,
+                    int64_t* fcalls, int64_t* nlaunches);
 
 /* ---- Cross-population request coalescer (8(b) "Threading") ----------------
  * The reference scores one tree per mutation from every population task concurrently

@@ -1,7 +1,8 @@
 // srhip_internal.h — library-internal declarations shared by the translation units of libsrhip.so
 // (srhip_host.cpp: program upload, datasets, evaluation driver, C ABI; srhip_compile.cpp: the tree
 // compiler, device-free; srhip_plan.cpp: the launch decision and the launch order, device-free;
-// srhip_optim.cpp: constant gradients and the batched BFGS constant optimizer).  Not part of the public ABI.
+// srhip_optim.cpp: constant gradients and the batched BFGS constant optimizer, whose state machine is
+// srhip_bfgs.cpp, device-free with a header of its own).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

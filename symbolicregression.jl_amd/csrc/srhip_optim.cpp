@@ -10,7 +10,10 @@
 //   start (Optim.Options(iterations = 8), src/Options.jl:691-705) from the current constants and from
 //   `nrestarts` perturbed starts x0 .* (1 + randn/2); a tree's constants are replaced only if the best
 //   minimum beats its baseline loss (:70-78).  Every tree runs its own state machine and each kernel
-//   launch evaluates the one point every still-active tree needs next (bfgs_pipelined).
+//   launch evaluates the one point every still-active tree needs next.  The state machine (BFGS, Newton,
+//   BackTracking, best of the starts, value-only trials, the speculative run-ahead) is the device-free
+//   unit srhip_bfgs.h / srhip_bfgs.cpp; this file holds its device evaluator (DeviceEvaluator: constants
+//   into the program, speculative slots, eval_grad) and the driver that joins the two (bfgs_pipelined).
 //   Differences from the reference, by design: exact (dual-number) gradients instead of Optim's
 //   finite differences, and Newton's Hessian as a central difference of those exact gradients instead
 //   of a second difference of losses -- parity is on the optimised loss, SURVEY.md 8(a) A13.
@@ -27,6 +30,7 @@
 #include <thread>
 #include <vector>
 
+#include "srhip_bfgs.h"
 #include "srhip_grad.h"
 #include "srhip_grad_lossx.h"
 #include "srhip_internal.h"
@@ -587,469 +591,132 @@ static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, 
 
 namespace {
 
-// LineSearches.jl BackTracking (order 3) state of one tree: a finite-value phase (halve alpha while
-// phi(alpha) is not finite, at most iterfinitemax = 52 times), then the sufficient-decrease phase
-// (cubic / quadratic interpolation, alpha shrunk into [0.1, 0.5] of its last value, at most
-// iterations = 1000 times; a non-finite phi there simply fails the test and is interpolated on).
-struct LineSearch {
-  double phi0, dphi0, a1, a2, phix0, phix1;
-  int iter = 0, iterfinite = 0;
-  bool armijo = false;  // the finite-value phase is over
-};
-constexpr int LS_ITERFINITEMAX = 52, LS_ITERATIONS = 1000;
-
-// next trial step after phi(a2) = phix1 failed the sufficient-decrease test
-double backtrack_step(LineSearch& s) {
-  const double rho_hi = 0.5, rho_lo = 0.1;
-  double a_tmp;
-  // LineSearches.jl's expressions with Julia's association (x^2 = x*x, x^3 = x*x*x as literal powers)
-  if (s.iter == 1) {
-    a_tmp = -(s.dphi0 * (s.a2 * s.a2)) / (2.0 * (s.phix1 - s.phi0 - s.dphi0 * s.a2));
-  } else {
-    const double a1sq = s.a1 * s.a1, a2sq = s.a2 * s.a2;
-    const double div = 1.0 / (a1sq * a2sq * (s.a2 - s.a1));
-    const double e1 = s.phix1 - s.phi0 - s.dphi0 * s.a2, e0 = s.phix0 - s.phi0 - s.dphi0 * s.a1;
-    const double a = (a1sq * e1 - a2sq * e0) * div;
-    const double b = (-(s.a1 * s.a1 * s.a1) * e1 + (s.a2 * s.a2 * s.a2) * e0) * div;
-    if (fabs(a) <= 2.220446049250313e-16) a_tmp = s.dphi0 / (2.0 * b);
-    else a_tmp = (-b + sqrt(std::max(b * b - 3.0 * a * s.dphi0, 0.0))) / (3.0 * a);
-  }
-  s.a1 = s.a2;
-  a_tmp = std::isnan(a_tmp) ? s.a2 * rho_hi : std::min(a_tmp, s.a2 * rho_hi);  // NaNMath.min
-  return std::max(a_tmp, s.a2 * rho_lo);
-}
-
-// one BackTracking step on phi(a2): LS_CONTINUE (next trial at the new a2), LS_ACCEPT, or a failure
-// that ends the start: LS_FAIL (iterations exhausted, LineSearchException) or LS_FAIL_NEGINF (the
-// slope overflowed to -Inf: phi0 + c1 a dphi0 = -Inf for every alpha > 0 the remaining iterations can
-// reach, so every further trial fails and BackTracking throws after exactly LS_ITERATIONS of them)
-enum { LS_CONTINUE = 0, LS_ACCEPT = 1, LS_FAIL = 2, LS_FAIL_NEGINF = 3 };
-int ls_update(LineSearch& L, double phi) {
-  L.phix1 = phi;
-  if (!L.armijo) {
-    if (!std::isfinite(phi) && L.iterfinite < LS_ITERFINITEMAX) {  // hard-coded halving until finite
-      L.iterfinite += 1;
-      L.a1 = L.a2;
-      L.a2 = L.a1 / 2.0;
-      return LS_CONTINUE;
-    }
-    L.armijo = true;
-  }
-  if (phi > L.phi0 + 1e-4 * L.a2 * L.dphi0) {  // sufficient decrease not met (or phi = Inf)
-    if (L.dphi0 == -INFINITY) return LS_FAIL_NEGINF;
-    if (++L.iter > LS_ITERATIONS) return LS_FAIL;
-    const double a2 = backtrack_step(L);
-    L.phix0 = L.phix1;
-    L.a2 = a2;
-    return LS_CONTINUE;
-  }
-  return LS_ACCEPT;
-}
-
-}  // namespace
-
-// All restarts of all trees as one pipelined batch.  Every tree runs its own state machine
-// (initial point -> [Hessian probes] -> line-search trials -> ... -> next restart); each launch
-// evaluates the one point every active tree needs next, so a tree never waits for a slower tree's
-// line search or restart.  A tree's loss and gradient do not depend on which other trees share the
-// launch (fixed row chunks, fixed reduction order), so each tree's trajectory -- and the outcome --
-// is the one it would follow optimised alone (tests/test_gpu_optim.py checks this bit for bit).
-//
-// BFGS (nconst >= 2): Optim's BFGS -- inverse-Hessian approximation from the identity, direction
-//   s = -H g (steepest descent if that is not a descent direction), update skipped unless
-//   dx'dg > 0.
-// Newton (nconst == 1, src/ConstantOptimization.jl:27-31): direction s = -g / |h| (Optim's
-//   cholesky!(Positive, H) of a 1x1 Hessian flips a negative curvature and replaces a zero one by
-//   1), h = (g(c + e) - g(c - e)) / 2e with e = cbrt(eps) max(1, |c|): two extra gradient launches
-//   per iteration ("Hessian probes", not counted as objective calls, as Optim counts h_calls apart).
-// Both: BackTracking line search from alpha = 1 (InitialStatic), stop on |g|_inf <= g_tol, on an
-//   unchanged objective (f_reltol = x_abstol = 0) or after `iterations` iterations.
-//
-// Speculative trial points (SRHIP_OPTIM_SPEC slots, default 256, 0 = off): a line search whose last
-// trial was non-finite usually keeps failing for many trials (an overflowing direction halves alpha
-// ~50 times, then shrinks it in the Armijo phase until x + a s rounds back to x -- hundreds of
-// launches for one tree at the pipeline's tail).  While few trees are active, the launch also
-// evaluates, in spare program slots (the tree's code with its constant immediates rewritten), the
-// next points the tree's BackTracking would try if every pending trial came back non-finite.  After
-// the launch they are consumed in order for as long as the line search really asks for exactly that
-// alpha (same line search, bitwise-equal alpha), so every consumed result is the one the sequential
-// pipeline would have launched for: trajectories, outcomes and objective-call counts are unchanged.
-static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss,
-                          const View& v, const std::vector<int32_t>& trees, const std::vector<int64_t>& coff,
-                          int iterations, double g_tol, const std::vector<std::vector<double>>& starts,
-                          std::vector<double>& best_x, std::vector<double>& best_f, std::vector<int64_t>& fcalls,
-                          const RowsetBatch* rb = nullptr) {
-  enum { INIT = 0, TRIAL = 1, DONE = 2, HESS_P = 3, HESS_M = 4, GRADAT = 5 };
-  const int nstarts = (int)starts.size();
-  const size_t nall = best_x.size();
-  std::vector<double> x(nall), g(nall), s(nall), xe(nall), fe(P->ntrees), ge(nall), f(P->ntrees, INFINITY);
-  std::vector<double> hstep(P->ntrees, 0.0), gplus(P->ntrees, 0.0), hcurv(P->ntrees, 1.0);
-  std::vector<int64_t> hoff(P->ntrees + 1, 0);
-  for (int32_t t = 0; t < P->ntrees; ++t) {
-    const int64_t n = coff[t + 1] - coff[t];
-    hoff[t + 1] = hoff[t] + n * n;
-  }
-  std::vector<double> H(hoff.back(), 0.0);
-  std::vector<int> phase(P->ntrees, DONE), start(P->ntrees, 0), iter(P->ntrees, 0);
-  std::vector<LineSearch> ls(P->ntrees);
-  // consecutive non-finite trials of the current line search, and a line-search generation counter
-  std::vector<int> nfstreak(P->ntrees, 0);
-  std::vector<int64_t> lsgen(P->ntrees, 0);
-  // the last two finite trial points (alpha, phi) of the current line search, newest first: the
-  // speculation's model of phi along the search direction
-  struct Hist {
-    int n = 0;
-    double a[2], f[2];
-  };
-  std::vector<Hist> hist(P->ntrees);
-  // per-tree speculation depth: doubled while every speculative point of a launch is consumed,
-  // cut back to what was consumed (+1) after a misprediction
-  std::vector<int> sdepth(P->ntrees, 4);
-  // value-only trial points (SRHIP_OPTIM_VALUE_TRIALS, default on): a line search's trials after its
-  // first are evaluated without tangents; an accepted one is re-evaluated with its gradient (phase
-  // GRADAT, same point, same loss bits, not an objective call)
+// The knobs of a run from the SRHIP_OPTIM_* switches, with their defaults and clamps (the state machine,
+// srhip_bfgs.cpp, reads no environment)
+BfgsKnobs bfgs_knobs(int iterations, double g_tol) {
+  BfgsKnobs k;
+  k.iterations = iterations;
+  k.g_tol = g_tol;
+  // value-only trial points (SRHIP_OPTIM_VALUE_TRIALS, default on)
   const char* vte = getenv("SRHIP_OPTIM_VALUE_TRIALS");
-  const bool value_trials = !(vte && *vte == '0');
-  std::vector<uint8_t> vonly(P->ntrees, 0);
-  std::vector<double> xacc(nall), phiacc(P->ntrees, 0.0);
-  for (size_t k = 0; k < nall; ++k) xe[k] = best_x[k];
-  auto newton = [&](int32_t t) { return coff[t + 1] - coff[t] == 1; };
-  auto gnorm = [&](int32_t t, const std::vector<double>& gg) {
-    double m = 0.0;
-    for (int64_t k = coff[t]; k < coff[t + 1]; ++k) m = std::max(m, fabs(gg[k]));
-    return m;
-  };
-  auto begin_start = [&](int32_t t) {
-    const int64_t n = coff[t + 1] - coff[t], o = coff[t];
-    for (int64_t k = o; k < o + n; ++k) x[k] = starts[start[t]][k];
-    for (int64_t i = 0; i < n; ++i)
-      for (int64_t j = 0; j < n; ++j) H[hoff[t] + i * n + j] = i == j ? 1.0 : 0.0;
-    phase[t] = INIT;
-  };
-  auto finish_start = [&](int32_t t) {
-    // the first start is `result` unconditionally (:50); a restart replaces it only if strictly
-    // better (:65-67)
-    if (start[t] == 0 || f[t] < best_f[t]) {
-      best_f[t] = f[t];
-      for (int64_t k = coff[t]; k < coff[t + 1]; ++k) best_x[k] = x[k];
-    }
-    if (++start[t] < nstarts) begin_start(t);
-    else phase[t] = DONE;
-  };
-  // Newton: probe the gradient at c + e and c - e for the curvature at the current point
-  auto begin_hess = [&](int32_t t) {
-    hstep[t] = 6.055454452393343e-06 * std::max(1.0, fabs(x[coff[t]]));  // cbrt(eps(Float64))
-    phase[t] = HESS_P;
-  };
-  // next iteration of t from (x, f, g): search direction and a fresh line search
-  auto begin_iter = [&](int32_t t) {
-    if (iter[t] >= iterations) {
-      finish_start(t);
-      return;
-    }
-    const int64_t n = coff[t + 1] - coff[t], o = coff[t];
-    double dphi = 0.0;
-    if (newton(t)) {
-      s[o] = -g[o] / hcurv[t];
-      dphi = g[o] * s[o];
-    } else {
-      for (int64_t i = 0; i < n; ++i) {
-        double acc = 0.0;
-        for (int64_t j = 0; j < n; ++j) acc += H[hoff[t] + i * n + j] * g[o + j];
-        s[o + i] = -acc;
-        dphi += g[o + i] * s[o + i];
-      }
-      if (!(dphi < 0.0)) {
-        dphi = 0.0;
-        for (int64_t i = 0; i < n; ++i) {
-          for (int64_t j = 0; j < n; ++j) H[hoff[t] + i * n + j] = i == j ? 1.0 : 0.0;
-          s[o + i] = -g[o + i];
-          dphi -= g[o + i] * g[o + i];
-        }
-      }
-    }
-    LineSearch& L = ls[t];
-    L = LineSearch();
-    L.phi0 = f[t];
-    L.dphi0 = dphi;
-    L.a1 = L.a2 = 1.0;  // InitialStatic: alpha = 1
-    L.phix0 = L.phix1 = f[t];
-    phase[t] = TRIAL;
-    nfstreak[t] = 0;
-    lsgen[t] += 1;
-    hist[t] = Hist();
-  };
-  auto next_iter = [&](int32_t t) {  // after an accepted step
-    iter[t] += 1;
-    if (newton(t) && iter[t] < iterations) begin_hess(t);
-    else begin_iter(t);
-  };
-  const char* tre = getenv("SRHIP_OPTIM_TRACE");
-  const int trace_tree = tre && *tre ? atoi(tre) : -1;
-  // one evaluation result of tree t at the point xv: loss phi, gradient gv
-  // an accepted step to (xv, phi) with gradient gv there: BFGS update, then converge or iterate
-  auto accept = [&](int32_t t, double phi, const double* gv, const double* xv) {
-    const int64_t o = coff[t], n = coff[t + 1] - coff[t];
-    const LineSearch& L = ls[t];
-    if (!newton(t)) {
-      std::vector<double> dx(n), dg(n), u(n);
-      double dxdg = 0.0;
-      for (int64_t i = 0; i < n; ++i) {
-        dx[i] = L.a2 * s[o + i];
-        dg[i] = gv[i] - g[o + i];
-        dxdg += dx[i] * dg[i];
-      }
-      if (dxdg > 0.0) {
-        double dgu = 0.0;
-        for (int64_t i = 0; i < n; ++i) {
-          double acc = 0.0;
-          for (int64_t j = 0; j < n; ++j) acc += H[hoff[t] + i * n + j] * dg[j];
-          u[i] = acc;
-          dgu += dg[i] * acc;
-        }
-        const double c1 = (dxdg + dgu) / (dxdg * dxdg), c2 = 1.0 / dxdg;
-        for (int64_t i = 0; i < n; ++i)
-          for (int64_t j = 0; j < n; ++j)
-            H[hoff[t] + i * n + j] += c1 * dx[i] * dx[j] - c2 * (u[i] * dx[j] + dx[i] * u[j]);
-      }
-    }
-    const double fold = f[t];
-    for (int64_t k = 0; k < n; ++k) {
-      x[o + k] = xv[k];
-      g[o + k] = gv[k];
-    }
-    f[t] = phi;
-    if (phi == fold || gnorm(t, g) <= g_tol) finish_start(t);  // converged
-    else next_iter(t);
-  };
-  // one evaluation result of tree t at the point xv: loss phi, gradient gv (nullptr: value only)
-  auto consume = [&](int32_t t, double phi, const double* gv, const double* xv) {
-    const int64_t o = coff[t], n = coff[t + 1] - coff[t];
-    if (t == trace_tree) {  // SRHIP_OPTIM_TRACE=<tree>: every evaluation of one tree, stderr
-      fprintf(stderr, "[srhip optim] tree %d start %d iter %d phase %d a %.17g f %.17g x", t, start[t], iter[t],
-              phase[t], phase[t] == TRIAL ? ls[t].a2 : 0.0, phi);
-      for (int64_t k = 0; k < n; ++k) fprintf(stderr, " %.17g", xv[k]);
-      fprintf(stderr, " g");
-      for (int64_t k = 0; k < n; ++k) fprintf(stderr, gv ? " %.17g" : " -", gv ? gv[k] : 0.0);
-      fprintf(stderr, "\n");
-    }
-    if (phase[t] == GRADAT) {  // the gradient at an accepted value-only trial point
-      accept(t, phiacc[t], gv, xacc.data() + o);
-      return;
-    }
-    if (phase[t] == HESS_P) {
-      gplus[t] = std::isfinite(phi) ? gv[0] : NAN;
-      phase[t] = HESS_M;
-      return;
-    }
-    if (phase[t] == HESS_M) {
-      const double h = std::isfinite(phi) ? (gplus[t] - gv[0]) / (2.0 * hstep[t]) : NAN;
-      hcurv[t] = (std::isfinite(h) && h != 0.0) ? fabs(h) : 1.0;  // cholesky!(Positive, [h])
-      begin_iter(t);
-      return;
-    }
-    fcalls[t] += 1;
-    if (phase[t] == INIT) {
-      f[t] = phi;
-      for (int64_t k = 0; k < n; ++k) g[o + k] = gv[k];
-      iter[t] = 0;
-      if (!std::isfinite(f[t]) || gnorm(t, g) <= g_tol) finish_start(t);
-      else if (newton(t) && iterations > 0) begin_hess(t);
-      else begin_iter(t);
-      return;
-    }
-    if (g_stats_on && !std::isfinite(phi)) g_nonfinite_trials += 1;
-    LineSearch& L = ls[t];
-    if (std::isfinite(phi)) {
-      Hist& h = hist[t];
-      h.a[1] = h.a[0];
-      h.f[1] = h.f[0];
-      h.a[0] = L.a2;
-      h.f[0] = phi;
-      h.n = std::min(h.n + 1, 2);
-    }
-    switch (ls_update(L, phi)) {
-      case LS_CONTINUE: nfstreak[t] = std::isfinite(phi) ? 0 : nfstreak[t] + 1; return;
-      case LS_FAIL_NEGINF: fcalls[t] += LS_ITERATIONS - L.iter; finish_start(t); return;  // counted, not launched
-      case LS_FAIL: finish_start(t); return;  // LineSearchException: the start ends at its last accepted point
-      default: break;
-    }
-    if (!gv) {  // accepted without a gradient: fetch it at this point next launch
-      for (int64_t k = 0; k < n; ++k) xacc[o + k] = xv[k];
-      phiacc[t] = phi;
-      phase[t] = GRADAT;
-      return;
-    }
-    accept(t, phi, gv, xv);
-  };
-  for (int32_t t : trees) begin_start(t);
+  k.value_trials = !(vte && *vte == '0');
+  // SRHIP_OPTIM_SPEC, default 32 slots: a launch of a few trees is latency-bound (one tree x 100k rows fills
+  // ~5 % of the wave slots), so a few dozen extra points cost little; more only adds mispredicted work
   const char* spe = getenv("SRHIP_OPTIM_SPEC");
-  // default 32 slots: a launch of a few trees is latency-bound (one tree x 100k rows fills ~5 % of
-  // the wave slots), so a few dozen extra points cost little; more only adds mispredicted work
-  const int spec_cap = spe && *spe ? std::max(0, std::min(atoi(spe), 4096)) : 32;
+  k.spec_slots = spe && *spe ? std::max(0, std::min(atoi(spe), 4096)) : 32;
   // speculate only in the pipeline's tail (SRHIP_OPTIM_SPEC_ACTIVE, default 64 active trees), at most
   // SRHIP_OPTIM_SPEC_DEPTH (default 64) points per tree and launch
-  const size_t SPEC_MAX_ACTIVE = (size_t)std::max(0, env_int("SRHIP_OPTIM_SPEC_ACTIVE", 64));
-  const int SPEC_MAX_DEPTH = std::max(1, env_int("SRHIP_OPTIM_SPEC_DEPTH", 64));
-  if (P->gspec_cap != spec_cap) {
-    P->gspec_cap = spec_cap;  // the next gradient compile allocates the slots (a full compile)
-    P->grad_ready = false;
-  }
-  struct Spec {
-    int32_t t, slot;
-    int64_t gen;
-    double alpha;
-    int64_t off;  // into sx / sg
-  };
-  std::vector<Spec> spec;
-  std::vector<double> sx, sg, sf;
-  std::vector<GradItem> sitems;
-  std::vector<int32_t> act;
-  for (;;) {
-    act.clear();
-    for (int32_t t : trees) {
-      if (phase[t] == DONE) continue;
-      act.push_back(t);
-      const int64_t o = coff[t], e = coff[t + 1];
-      switch (phase[t]) {
-        case INIT: for (int64_t k = o; k < e; ++k) xe[k] = x[k]; break;
-        case TRIAL: for (int64_t k = o; k < e; ++k) xe[k] = x[k] + ls[t].a2 * s[k]; break;
-        case HESS_P: xe[o] = x[o] + hstep[t]; break;
-        case HESS_M: xe[o] = x[o] - hstep[t]; break;
-        case GRADAT: for (int64_t k = o; k < e; ++k) xe[k] = xacc[k]; break;
-        default: break;
-      }
-      // trials after a line search's first: loss only
-      vonly[t] = value_trials && phase[t] == TRIAL && ls[t].iter + ls[t].iterfinite >= 1;
-    }
-    if (act.empty()) break;
-    const double t0 = now_s();
-    for (int32_t t : act) {  // only the active trees' constants change (get_constants order per tree)
-      const double* c = xe.data() + coff[t];
+  k.spec_max_active = std::max(0, env_int("SRHIP_OPTIM_SPEC_ACTIVE", 64));
+  k.spec_max_depth = std::max(1, env_int("SRHIP_OPTIM_SPEC_DEPTH", 64));
+  const char* tre = getenv("SRHIP_OPTIM_TRACE");  // SRHIP_OPTIM_TRACE=<tree>: every evaluation of one tree, stderr
+  k.trace_tree = tre && *tre ? atoi(tre) : -1;
+  k.stats_on = g_stats_on;  // SRHIP_OPTIM_TIMING=2 / 3, as the entry point read it for this thread
+  return k;
+}
+
+// bfgs_run's evaluator on the device: each launch's points become the active trees' constants, the granted
+// speculative points go to spare program slots (the tree's code with its constant immediates rewritten),
+// and one eval_grad evaluates both (on the view's rows, or every tree on its own row set: rb)
+struct DeviceEvaluator {
+  srhip_ctx* ctx;
+  const srhip_dataset* ds;
+  srhip_program* P;
+  const LossSel& loss;
+  const View& v;
+  const RowsetBatch* rb;
+  std::vector<GradItem> sitems = {};
+  int64_t spec_lo = INT64_MAX, spec_hi = -1;  // the instructions the launch's slots rewrote
+  double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+
+  int place(const BfgsBatch& b) {
+    t0 = now_s();
+    for (int32_t t : b.act) {  // only the active trees' constants change (get_constants order per tree)
+      const double* c = b.xe.data() + b.coff[t];
       set_consts(P->nodes.data() + P->offsets[t], 0, c);
     }
     // the patch scans just the trees whose constants moved (a union if an earlier hint is pending;
     // no hint at all -- an unknown change -- keeps the full scan)
-    if (P->grad_ready) P->ghint = act;
-    else if (!P->ghint.empty()) P->ghint.insert(P->ghint.end(), act.begin(), act.end());
+    if (P->grad_ready) P->ghint = b.act;
+    else if (!P->ghint.empty()) P->ghint.insert(P->ghint.end(), b.act.begin(), b.act.end());
     P->grad_ready = false;
-    // speculative points of trees in a non-finite streak (instantiated after the compile / patch:
-    // a full compile resets the slot region)
-    spec.clear();
+    spec_lo = INT64_MAX;
+    spec_hi = -1;
+    return SRHIP_OK;
+  }
+  // the slots are instantiated after the compile / patch: a full compile resets the slot region
+  int slots(int* n) {
+    const double tc = now_s();
+    const int rc = compile_grad_program(*P);
+    g_t_compile += now_s() - tc;
+    *n = P->gspec_alloc;
+    return rc;
+  }
+  bool grant(int32_t slot, int32_t t, const double* xs) {
+    bool sfail = false;
+    return spec_instantiate(*P, slot, t, xs, &sfail, spec_lo, spec_hi);
+  }
+  int evaluate(BfgsBatch& b) {
     sitems.clear();
-    int64_t spec_lo = INT64_MAX, spec_hi = -1;
-    if (spec_cap > 0 && act.size() <= SPEC_MAX_ACTIVE) {
-      // a line search that has already failed twice is likely to keep backtracking
-      auto candidate = [&](int32_t t) {
-        return phase[t] == TRIAL && ls[t].iter + ls[t].iterfinite >= 2;
-      };
-      int ncand = 0;
-      for (int32_t t : act) ncand += candidate(t);
-      if (ncand > 0) {
-        const double tc = now_s();
-        int rc = compile_grad_program(*P);
-        g_t_compile += now_s() - tc;
-        if (rc) return rc;
-        int slot = 0;
-        int64_t off = 0;
-        for (int32_t t : act) {
-          const int depth = std::min(std::min(sdepth[t], SPEC_MAX_DEPTH), P->gspec_alloc - slot);
-          if (depth < 1 || !candidate(t)) continue;
-          // the line search run ahead on predicted values: non-finite again after a non-finite
-          // trial; otherwise phi(a) = phi0 + d (a / a_k)^q through the last two finite points (q = 2
-          // from one).  Only the alphas matter, and BackTracking's steps are mostly its clamps
-          // (0.5 or 0.1 of the last alpha), which a rough model reproduces bit for bit.
-          const Hist& h = hist[t];
-          const double phi0 = ls[t].phi0;
-          double q = 2.0;
-          if (h.n == 2 && h.f[0] > phi0 && h.f[1] > phi0 && h.a[0] != h.a[1] && h.a[0] > 0.0 && h.a[1] > 0.0)
-            q = log((h.f[1] - phi0) / (h.f[0] - phi0)) / log(h.a[1] / h.a[0]);
-          const bool model = nfstreak[t] == 0 && h.n > 0 && h.f[0] > phi0 && h.a[0] > 0.0 && std::isfinite(q);
-          if (nfstreak[t] == 0 && !model) continue;
-          LineSearch Ls = ls[t];
-          for (int j = 0; j < depth; ++j) {
-            const double phi_pred = model ? phi0 + (h.f[0] - phi0) * pow(Ls.a2 / h.a[0], q) : INFINITY;
-            if (ls_update(Ls, phi_pred) != LS_CONTINUE) break;
-            spec.push_back(Spec{t, slot++, lsgen[t], Ls.a2, off});
-            off += coff[t + 1] - coff[t];
-          }
-        }
-        sx.resize(off);
-        sg.resize(off);
-        sf.resize(spec.size());
-        size_t keep = 0;
-        int32_t dead = -1;  // a tree whose chain broke (slot instantiation refused): drop its rest
-        for (size_t i = 0; i < spec.size(); ++i) {
-          const Spec& q = spec[i];
-          if (q.t == dead) continue;
-          const int64_t o = coff[q.t], n = coff[q.t + 1] - o;
-          for (int64_t k = 0; k < n; ++k) sx[q.off + k] = x[o + k] + q.alpha * s[o + k];
-          bool sfail = false;
-          if (!spec_instantiate(*P, q.slot, q.t, sx.data() + q.off, &sfail, spec_lo, spec_hi)) {
-            dead = q.t;
-            continue;
-          }
-          spec[keep++] = q;
-        }
-        spec.resize(keep);
-        for (size_t i = 0; i < spec.size(); ++i)
-          sitems.push_back(GradItem{P->ntrees + spec[i].slot, spec[i].t, &sf[i], sg.data() + spec[i].off, nullptr,
-                                    value_trials});
-        g_spec_launched += (int64_t)spec.size();
-      }
-    }
-    const double t1 = now_s();
-    int rc = eval_grad(ctx, ds, P, loss, v, act, coff, fe.data(), ge.data(), nullptr, &sitems, spec_lo, spec_hi,
-                       vonly.data(), /*timed=*/false, rb);
+    for (size_t i = 0; i < b.spec.size(); ++i)
+      sitems.push_back(GradItem{P->ntrees + b.spec[i].slot, b.spec[i].t, &b.sf[i], b.sg.data() + b.spec[i].off, nullptr,
+                                b.knobs.value_trials});
+    t1 = now_s();
+    const int rc = eval_grad(ctx, ds, P, loss, v, b.act, b.coff, b.fe.data(), b.ge.data(), nullptr, &sitems, spec_lo,
+                             spec_hi, b.vonly.data(), /*timed=*/false, rb);
     if (rc) return rc;
     if (loss.expr) {
       // an expression's loss is no failure where it is not finite (did_succeed is the tree's alone), so NaN and
       // -Inf reach here: they count as +Inf before the line search or the acceptance sees them (ls_update
       // compares with >, which a NaN would pass; BackTracking shrinks on !isfinite)
-      for (int32_t t : act)
-        if (!std::isfinite(fe[t])) fe[t] = INFINITY;
-      for (double& sfv : sf)
+      for (int32_t t : b.act)
+        if (!std::isfinite(b.fe[t])) b.fe[t] = INFINITY;
+      for (double& sfv : b.sf)
         if (!std::isfinite(sfv)) sfv = INFINITY;
     }
-    if (g_stats_on)  // SRHIP_OPTIM_TIMING=2: launch-size histogram
-      g_hist[act.size() <= 1 ? 0 : act.size() <= 4 ? 1 : act.size() <= 16 ? 2 : act.size() <= 64 ? 3 : 4] += 1;
-    const double t2 = now_s();
+    t2 = now_s();
     g_t_host += t1 - t0;
     g_t_eval += t2 - t1;
-    size_t si = 0;
-    int64_t used_all = 0;
-    for (int32_t t : act) {
-      const int64_t o = coff[t];
-      consume(t, fe[t], vonly[t] ? nullptr : ge.data() + o, xe.data() + o);
-      // then t's speculative points, in order, while its line search asks for exactly them
-      int launched = 0, used = 0;
-      bool hit = true;
-      for (; si < spec.size() && spec[si].t == t; ++si) {
-        const Spec& q = spec[si];
-        launched += 1;
-        hit = hit && phase[t] == TRIAL && lsgen[t] == q.gen && memcmp(&ls[t].a2, &q.alpha, sizeof(double)) == 0;
-        if (!hit) continue;
-        consume(t, sf[si], value_trials ? nullptr : sg.data() + q.off, sx.data() + q.off);
-        used += 1;
-      }
-      used_all += used;
-      if (launched > 0) {
-        g_spec_used += used;
-        // all used and still searching: go deeper; else keep what would have been used (+1)
-        sdepth[t] = used == launched && phase[t] == TRIAL ? std::min(2 * sdepth[t], SPEC_MAX_DEPTH)
-                                                          : std::max(1, std::min(sdepth[t], used + 1));
-      }
-    }
-    if (g_launch_log) {
-      int nv = 0, ntrial = 0;
-      for (int32_t t : act) {
-        nv += vonly[t];
-        ntrial += phase[t] == TRIAL;
-      }
-      fprintf(stderr, "srhip launch: t %.3f act %zu trial %d vonly %d spec %zu used %lld host %.3f eval %.3f ms\n",
-              1e3 * t2, act.size(), ntrial, nv, spec.size(), (long long)used_all, 1e3 * (t1 - t0), 1e3 * (t2 - t1));
-    }
+    return SRHIP_OK;
   }
+  void launched(const BfgsBatch& b) {
+    if (!g_launch_log) return;  // SRHIP_OPTIM_TIMING=3
+    int nv = 0;
+    for (int32_t t : b.act) nv += b.vonly[t];
+    fprintf(stderr, "srhip launch: t %.3f act %zu trial %d vonly %d spec %zu used %lld host %.3f eval %.3f ms\n",
+            1e3 * t2, b.act.size(), b.trials_pending(), nv, b.spec.size(), (long long)b.spec_used_last, 1e3 * (t1 - t0),
+            1e3 * (t2 - t1));
+  }
+};
+
+}  // namespace
+
+// All restarts of all trees as one pipelined batch.  Every tree runs its own state machine
+// (initial point -> [Hessian probes] -> line-search trials -> ... -> next restart: BfgsBatch,
+// srhip_bfgs.cpp); each launch evaluates the one point every active tree needs next, so a tree never
+// waits for a slower tree's line search or restart.  A tree's loss and gradient do not depend on which
+// other trees share the launch (fixed row chunks, fixed reduction order), so each tree's trajectory --
+// and the outcome -- is the one it would follow optimised alone (tests/test_gpu_optim.py checks this bit
+// for bit).  Speculative trial points (SRHIP_OPTIM_SPEC slots, default 32, 0 = off): while few trees are
+// active, the launch also evaluates, in spare program slots, the next points a failing line search would
+// try; a result is consumed only where the line search really asks for exactly that point.
+static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss,
+                          const View& v, const std::vector<int32_t>& trees, const std::vector<int64_t>& coff,
+                          int iterations, double g_tol, const std::vector<std::vector<double>>& starts,
+                          std::vector<double>& best_x, std::vector<double>& best_f, std::vector<int64_t>& fcalls,
+                          const RowsetBatch* rb = nullptr) {
+  const BfgsKnobs knobs = bfgs_knobs(iterations, g_tol);
+  BfgsBatch batch(P->ntrees, trees, coff, starts, knobs, best_x, best_f, fcalls);
+  if (P->gspec_cap != knobs.spec_slots) {
+    P->gspec_cap = knobs.spec_slots;  // the next gradient compile allocates the slots (a full compile)
+    P->grad_ready = false;
+  }
+  DeviceEvaluator ev{ctx, ds, P, loss, v, rb};
+  const int rc = bfgs_run(batch, ev);
+  g_nonfinite_trials += batch.stats.nonfinite_trials;
+  g_spec_launched += batch.stats.spec_launched;
+  g_spec_used += batch.stats.spec_used;
+  for (int i = 0; i < 5; ++i) g_hist[i] += batch.stats.hist[i];
+  if (rc) return rc;
   if (g_stats_on) {  // the trees with the most objective calls (the pipeline's tail)
     std::vector<int32_t> by(trees);
     std::sort(by.begin(), by.end(), [&](int32_t a, int32_t b) { return fcalls[a] > fcalls[b]; });
@@ -1369,6 +1036,27 @@ void report_fcalls(const std::vector<int64_t>& fcalls, const uint8_t* out_improv
   if (!out_fcalls) return;
   for (size_t t = 0; t < fcalls.size(); ++t) out_fcalls[t] = fcalls[t] + out_improved[t];
 }
+// a failed step (status rc) whose call must leave the constants as they came: restored, the step's message kept
+int restore_and_reraise(srhip_program& P, const std::vector<double>& x0, int rc) {
+  const std::string msg = last_error();
+  restore_constants(P, x0);
+  return fail(rc, "%s", msg.c_str());
+}
+// The entry points' common end: install the accepted constants, re-score the returned trees with the call's
+// evaluator (the reference re-scores accepted members), report the calls.  A failed re-score under a loss
+// expression (expr) leaves the constants as they came.
+template <class Score>
+int install_and_rescore(srhip_program& P, bool expr, const std::vector<double>& x0, const std::vector<double>& final_x,
+                        Score score, double* out_loss, const std::vector<int64_t>& fcalls, const uint8_t* out_improved,
+                        int64_t* out_fcalls) {
+  int rc = install_constants(P, final_x);
+  if (rc) return rc;
+  std::vector<uint8_t> ok(P.ntrees);
+  rc = score(out_loss, ok.data());
+  if (rc) return expr ? restore_and_reraise(P, x0, rc) : rc;
+  report_fcalls(fcalls, out_improved, out_fcalls);
+  return SRHIP_OK;
+}
 
 }  // namespace
 
@@ -1446,21 +1134,7 @@ int optimize_starts(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, c
     }
   }
   const std::vector<double> final_x = accept_against_baseline(x0, coff, best_x, best_f, base, out_improved);
-  rc = install_constants(*P, final_x);
-  if (rc) return rc;
-  // the loss of the returned trees, by the evaluator (the reference re-scores accepted members)
-  std::vector<uint8_t> ok(nt);
-  rc = score(out_loss, ok.data());
-  if (rc) {
-    if (loss.expr) {  // a failed call leaves the constants as they came
-      const std::string msg = last_error();
-      restore_constants(*P, x0);
-      return fail(rc, "%s", msg.c_str());
-    }
-    return rc;
-  }
-  report_fcalls(fcalls, out_improved, out_fcalls);
-  return SRHIP_OK;
+  return install_and_rescore(*P, loss.expr != nullptr, x0, final_x, score, out_loss, fcalls, out_improved, out_fcalls);
 }
 
 extern "C" {
@@ -1759,27 +1433,13 @@ int optimize_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, 
       }
       srhip_program_destroy(Q);
     }
-    if (rc) {
-      const std::string msg = last_error();
-      restore_constants(*P, x0);
-      return fail(rc, "%s", msg.c_str());
-    }
+    if (rc) return restore_and_reraise(*P, x0, rc);
   }
-  rc = install_constants(*P, final_x);
+  // the re-score: one rowsets launch
+  auto score = [&](double* l, uint8_t* ok) { return loss.score(ctx, ds, P, row_offsets, rows, l, ok); };
+  rc = install_and_rescore(*P, loss.expr != nullptr, x0, final_x, score, out_loss, fcalls, out_improved, out_fcalls);
   if (rc) return rc;
-  // the loss of the returned trees, by the evaluator (the reference re-scores accepted members): one launch
-  std::vector<uint8_t> ok(nt);
-  rc = loss.score(ctx, ds, P, row_offsets, rows, out_loss, ok.data());
-  if (rc) {
-    if (loss.expr) {  // a failed call leaves the constants as they came
-      const std::string msg = last_error();
-      restore_constants(*P, x0);
-      return fail(rc, "%s", msg.c_str());
-    }
-    return rc;
-  }
   ctx->rowsets_fallback = (int64_t)alone.size();
-  report_fcalls(fcalls, out_improved, out_fcalls);
   return SRHIP_OK;
 }
 

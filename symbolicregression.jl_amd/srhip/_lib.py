@@ -74,6 +74,20 @@ class PlanInfo(ctypes.Structure):  # struct srhip_plan_info
         "fused", "hot", "pad")] + [("lds", ctypes.c_int64)]
 
 
+class BfgsQuery(ctypes.Structure):  # struct srhip_bfgs_query
+    _fields_ = [("ntrees", ctypes.c_int32), ("nstarts", ctypes.c_int32), ("const_offsets", ctypes.c_void_p),
+                ("starts", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in (
+                    "iterations", "value_trials", "spec_slots", "spec_max_active", "spec_max_depth", "pad")] + [
+                        ("g_tol", ctypes.c_double)]
+
+
+# srhip_bfgs_eval_fn: (user, nitems, tree, x_off, x, value_only, f, g) -> status
+BFGS_EVAL_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double),
+                                ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_double),
+                                ctypes.POINTER(ctypes.c_double))
+
+
 class SrhipError(RuntimeError):
     """A nonzero status from libsrhip (message from srhip_last_error)."""
 
@@ -170,6 +184,8 @@ SIGNATURES = {
     "srhip_code_cache_stats": (ctypes.c_int, [ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "srhip_tail_share_parts": (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp]),
     "srhip_plan_eval": (ctypes.c_int, [ctypes.POINTER(PlanQuery), ctypes.POINTER(PlanInfo)]),
+    "srhip_bfgs_host": (ctypes.c_int, [ctypes.POINTER(BfgsQuery), BFGS_EVAL_FN, _vp, _vp, _vp, _vp,
+                                       ctypes.POINTER(_i64)]),
 }
 
 _lib = None
