@@ -275,6 +275,13 @@ int srhip_eval_precise_partials(srhip_ctx* ctx, const srhip_dataset* ds, const s
                                 int32_t ntrees_sel, double* opsums);
 int srhip_precise_finalize(const srhip_program* prog, const int32_t* trees, int32_t ntrees_sel,
                            const double* opsums, uint8_t* out_ok);
+/* (diagnostic, no device) The decision of tree `tree` evaluated alone on a row set of its own, as
+ * srhip_eval_loss_rowsets takes it per tree: rows of the set, feat_stats[3 f ..] = {column sum (Float64
+ * data: sum of x * 2^-64), non-finite count (> 0: some), max |x| over the finite entries} of feature f over
+ * the set, chk_raw the interpreter's check statistic.  *out_status: 0 ok, 1 fail, 2 undecided; *out_chk
+ * (nullable): the statistic decided on (Float32: raised to the tree's +/- bound over the set's features). */
+int srhip_decide_rowset(const srhip_program* prog, int32_t tree, int64_t nfeatures, int64_t rows,
+                        const double* feat_stats, double chk_raw, uint8_t* out_status, double* out_chk);
 int srhip_chk_reduce_op(int dtype);
 int32_t srhip_program_max_ops(const srhip_program* prog);
 

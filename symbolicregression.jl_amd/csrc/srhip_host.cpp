@@ -24,6 +24,7 @@
 
 #include "../../include/srhip.h"
 #include "srhip_internal.h"
+#include "srhip_decide.h"
 #include "srhip_isa.h"
 #include "srhip_kernels.h"
 #include "srhip_lossx.h"
@@ -89,6 +90,22 @@ static void set_prog_pointers(const srhip_program& P) {
   P.sbound_dev = P.sbound.empty() ? nullptr : (const float*)(d + P.blob_off[5]);
 }
 
+// The program's host image (upload_program built it) and, behind it, an order tail (nullable) into d_prog
+// in one copy on stream st; the sections' device pointers, and ord_dev at the tail if there is one
+static int push_program_image(const srhip_program& P, const std::vector<int32_t>* tail, hipStream_t st) {
+  const size_t base = P.blob_off[6], bytes = tail ? tail->size() * sizeof(int32_t) : 0;
+  if (tail) {
+    P.blob.resize(base + bytes);
+    memcpy(P.blob.data() + base, tail->data(), bytes);
+  }
+  HIP_TRY(P.d_prog.ensure(base + bytes));
+  HIP_TRY(hipMemcpyAsync(P.d_prog.p, P.blob.data(), base + bytes, hipMemcpyHostToDevice, st));
+  set_prog_pointers(P);
+  P.upload_pending = false;
+  if (tail) P.ord_dev = (const uint8_t*)P.d_prog.p + base;
+  return SRHIP_OK;
+}
+
 int srhip::upload_program(srhip_program& P, bool sync, bool defer, hipStream_t stream) {
   HIP_TRY(hipSetDevice(P.ctx->device));
   // one host image and one copy (each hipMemcpyAsync costs a few us of API time and a blit on the
@@ -117,20 +134,11 @@ int srhip::upload_program(srhip_program& P, bool sync, bool defer, hipStream_t s
     P.upload_pending = true;
     return SRHIP_OK;
   }
-  P.upload_pending = false;
   // a launch order planned at creation (plan_persistent_order) travels in the same copy
   const bool with_order = !P.ord_host.empty() && P.ord_key[0] > 0;
-  const size_t nbytes = with_order ? total + P.ord_host.size() * sizeof(int32_t) : total;
-  if (with_order) {
-    P.blob.resize(nbytes);
-    memcpy(P.blob.data() + total, P.ord_host.data(), P.ord_host.size() * sizeof(int32_t));
-    h = P.blob.data();
-  }
-  HIP_TRY(P.d_prog.ensure(nbytes));
   hipStream_t st = stream ? stream : P.ctx->stream;
-  HIP_TRY(hipMemcpyAsync(P.d_prog.p, h, nbytes, hipMemcpyHostToDevice, st));
-  set_prog_pointers(P);
-  if (with_order) P.ord_dev = (const uint8_t*)P.d_prog.p + total;
+  const int rc = push_program_image(P, with_order ? &P.ord_host : nullptr, st);
+  if (rc) return rc;
   if (sync) HIP_TRY(hipStreamSynchronize(st));
   return SRHIP_OK;
 }
@@ -180,100 +188,6 @@ int srhip::make_view(srhip_ctx* ctx, const srhip_dataset* ds, const int64_t* idx
   v.sum_w = 0.0;  // (gathered_weight_sum fills it for the callers that need it)
   return SRHIP_OK;
 }
-
-namespace {
-
-// ---- the did_succeed decision, from (possibly all-reduced) partials ----------------------------
-// Partials layout (the C ABI's srhip_eval_loss_partials): sums[2t] = sum of (w *) l over the rows,
-// sums[2t+1] = sum of w (unweighted: the row count); sums[2T + 2f] = feature f column sum (Float64
-// data: sum of x * 2^-64), sums[2T + 2f + 1] = its non-finite count; sums[2T + 2F] = rows.  Every
-// entry combines across row shards by addition; chk[t] (the operator-output check statistic)
-// combines by max for Float32 (max |v|) and by addition for Float64 (sum of |v| 2^-512).
-
-// Returns 0 ok, 1 fail, 2 undecided (needs the precise pass).
-static int decide_info(const TreeInfo& I, int dtype, int32_t T, int64_t nfeat, const double* sums, double chk) {
-  if (I.static_fail) return 1;
-  if (dtype == SRHIP_I32) return 0;
-  const long double m = (long double)sums[2 * (size_t)T + 2 * (size_t)nfeat];
-  const long double ovf = ovf_threshold(dtype);
-  for (double c : I.fill_consts)
-    if ((long double)fabs(c) * m >= ovf) return 1;
-  for (int f : I.feat_checks) {
-    const double fsum = sums[2 * (size_t)T + 2 * (size_t)f], fbad = sums[2 * (size_t)T + 2 * (size_t)f + 1];
-    if (fbad > 0) return 1;
-    const long double sum = dtype == SRHIP_F64 ? (long double)fsum * 0x1p64L : (long double)fsum;
-    if (!isfinite(fsum) || fabsl(sum) >= ovf) return 1;
-  }
-  if (I.op_sumcheck.empty()) return 0;
-  if (!isfinite(chk)) return 1;  // a NaN / Inf operator output
-  long double bound;
-  if (dtype == SRHIP_F64) bound = (long double)chk * 0x1p512L;  // sum |v|
-  else bound = (long double)chk * m;                              // m * max |v|
-  if (bound * 2.0L >= ovf) return 2;
-  return 0;
-}
-
-// decide_info on the compact record: the same answer (fill constants: |c| m >= OVF is monotone in
-// |c|, so the largest decides; NaN never fails; the feature checks in any order)
-static int decide_fast(const srhip_program& P, int32_t t, int64_t nfeat, const double* sums, double chk) {
-  const TreeDecide& d = P.dec[t];
-  if (d.slow) return decide_info(P.info[t], P.dtype, P.ntrees, nfeat, sums, chk);
-  if (d.static_fail) return 1;
-  const int dtype = P.dtype;
-  if (dtype == SRHIP_I32) return 0;
-  const int32_t T = P.ntrees;
-  const long double m = (long double)sums[2 * (size_t)T + 2 * (size_t)nfeat];
-  const long double ovf = ovf_threshold(dtype);
-  if (d.maxc >= 0.0 && (long double)d.maxc * m >= ovf) return 1;
-  for (uint64_t fm = d.feat_mask; fm; fm &= fm - 1) {
-    const int f = __builtin_ctzll(fm);
-    const double fsum = sums[2 * (size_t)T + 2 * (size_t)f], fbad = sums[2 * (size_t)T + 2 * (size_t)f + 1];
-    if (fbad > 0) return 1;
-    const long double sum = dtype == SRHIP_F64 ? (long double)fsum * 0x1p64L : (long double)fsum;
-    if (!isfinite(fsum) || fabsl(sum) >= ovf) return 1;
-  }
-  if (!d.has_op) return 0;
-  if (!isfinite(chk)) return 1;
-  long double bound;
-  if (dtype == SRHIP_F64) bound = (long double)chk * 0x1p512L;
-  else bound = (long double)chk * m;
-  if (bound * 2.0L >= ovf) return 2;
-  return 0;
-}
-
-static void finalize(const srhip_program& P, int64_t nfeat, const double* sums, const double* chk, double* out_loss,
-                     uint8_t* out_ok, uint8_t* out_status) {
-  const bool fast = P.dec.size() == (size_t)P.ntrees && !env_flag("SRHIP_DECIDE_SLOW");
-  for (int32_t t = 0; t < P.ntrees; ++t) {
-    const double c = chk ? chk[t] : 0.0;
-    const int st = fast ? decide_fast(P, t, nfeat, sums, c) : decide_info(P.info[t], P.dtype, P.ntrees, nfeat, sums, c);
-    if (out_status) out_status[t] = (uint8_t)st;
-    if (out_ok) out_ok[t] = st == 0 ? 1 : 0;
-    if (out_loss) out_loss[t] = st == 0 ? sums[2 * (size_t)t] / sums[2 * (size_t)t + 1] : INFINITY;
-  }
-}
-
-// opsums[u][k]: exact-ish (f64) sum over all rows of operator output k of tree trees[u]
-static void finalize_precise(const srhip_program& P, const int32_t* trees, int32_t nsel, const double* opsums,
-                             uint8_t* out_ok, bool grad = false) {
-  const int stride = std::max(1, grad ? P.gmax_ops : P.max_ops);
-  const long double ovf = ovf_threshold(P.dtype);
-  for (int u = 0; u < nsel; ++u) {
-    const TreeInfo& I = grad ? P.ginfo[trees[u]] : P.info[trees[u]];
-    int st = I.static_fail ? 1 : 0;
-    for (size_t k = 0; k < I.op_sumcheck.size() && !st; ++k) {
-      const double s = opsums[(size_t)u * stride + k];
-      if (!isfinite(s)) st = 1;
-      else if (I.op_sumcheck[k]) {
-        const long double S = P.dtype == SRHIP_F64 ? (long double)s * 0x1p64L : (long double)s;
-        if (fabsl(S) >= ovf) st = 1;
-      }
-    }
-    out_ok[u] = st == 0 ? 1 : 0;
-  }
-}
-
-}  // namespace
 
 // ---- the device-allocation cache behind PoolBuf ----------------------------------------------
 namespace {
@@ -343,10 +257,6 @@ int srhip::next_fail_epoch(srhip_ctx* ctx, int64_t n, int32_t** flags, int32_t* 
   return SRHIP_OK;
 }
 
-int srhip::decide_tree(const TreeInfo& I, const srhip_program& P, int64_t nfeat, const double* sums, double chk) {
-  return decide_info(I, P.dtype, P.ntrees, nfeat, sums, chk);
-}
-
 int srhip::check_eval_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode,
                            const srhip_loss* loss) {
   if (!ctx || !ds || !P) return fail(SRHIP_ERR_INVALID, "null handle");
@@ -386,12 +296,7 @@ int srhip::check_loss_expr_args(srhip_ctx* ctx, const srhip_dataset* ds, const s
 
 // run_eval's device-decided precise pass: the reduction lists the trees whose overflow bound needs
 // the precise pass, and the precise launch + its reduction follow on the stream before the one host
-// synchronisation (no host round trip between the main launch and the precise pass)
-constexpr int32_t DEV_PRECISE_MAX = 64;
-// h_pout = [count, list (DEV_PRECISE_MAX) | pad to 8 bytes | per-operator sums (double)]: the sums start on
-// an 8-byte boundary (they followed the 65 ints directly, at byte 260: misaligned double stores on the
-// device and loads on the host -- UBSan's report from tools/host_stress, round 6)
-constexpr size_t PREC_SUMS_OFF = ((size_t)(1 + DEV_PRECISE_MAX) * sizeof(int32_t) + 7) & ~(size_t)7;
+// synchronisation (no host round trip between the main launch and the precise pass); its output: PreciseOut
 struct DevPrecise {
   bool used = false;
   int32_t count = 0;             // trees the device listed (may exceed DEV_PRECISE_MAX)
@@ -444,8 +349,7 @@ static int ensure_dev_precise(srhip_ctx* ctx, const srhip_program* P, const View
   const size_t per_tree = precise_per_tree(P, v, &sa);
   *cap = precise_cap(P, v, *cap);
   HIP_TRY(ctx->slab_prec.ensure((size_t)*cap * per_tree));
-  HIP_TRY(rs->h_pout.ensure(PREC_SUMS_OFF +
-                            (size_t)DEV_PRECISE_MAX * sa * sizeof(double), hipHostMallocCoherent));
+  HIP_TRY(rs->h_pout.ensure(PreciseOut::bytes(sa), hipHostMallocCoherent));
   return SRHIP_OK;
 }
 static int enqueue_dev_precise(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const View& v,
@@ -488,10 +392,9 @@ static int enqueue_dev_precise(srhip_ctx* ctx, const srhip_dataset* ds, const sr
   q.block_stride = 1;
   HIP_TRY(launch_eval(dtype, q, Rp, K_MAX, MODE_PRECISE, false, dim3(std::min(Lp.nrb, PRECISE_GRID_X), G), 16,
                       ctx->stream));
-  int32_t* hl = (int32_t*)rs->h_pout.p;
-  double* hs = (double*)((uint8_t*)rs->h_pout.p + PREC_SUMS_OFF);
-  HIP_TRY(launch_precise_reduce((const double*)ctx->slab_prec.p, Lp.nrb, stride, ulist, cap, G, DEV_PRECISE_MAX, hl,
-                                hs, ctx->stream));
+  const PreciseOut out{rs->h_pout.p};
+  HIP_TRY(launch_precise_reduce((const double*)ctx->slab_prec.p, Lp.nrb, stride, ulist, cap, G, DEV_PRECISE_MAX,
+                                out.head(), out.sums(), ctx->stream));
   *out_stride = stride;
   return SRHIP_OK;
 }
@@ -508,20 +411,8 @@ struct EvalJob {
   std::vector<int32_t> live;
   UndecidedList ul;
   DevBuf pred;  // MODE_PRED's device output (synchronous calls only)
-  float fbound = 0.0f;  // Float32: the features' max |x| (the +/- bound's F)
+  float fbound = 0.0f;  // Float32: the features' max |x| (feature_bound: the +/- bound's F)
 };
-// the features' max |x| over a view's rows (+Inf if any entry is non-finite), rounded up to Float32:
-// the F of the Float32 interpreter's +/- bound (EvalArgs::fbound)
-static float feature_bound(const View& v, int64_t nfeat) {
-  double F = 0.0;
-  for (int64_t f = 0; v.stats && f < nfeat; ++f) {
-    if (v.stats[f].nonfinite > 0 || !(v.stats[f].maxabs < INFINITY)) return INFINITY;
-    F = std::max(F, v.stats[f].maxabs);
-  }
-  if (!v.stats && nfeat > 0) return INFINITY;
-  const float r = (float)F;
-  return (double)r >= F ? r : std::nextafter(r, INFINITY);
-}
 
 // What plan_eval reads of a context and a program with nlive live trees (in EvalPlanIn's order): an
 // unweighted, unsharded MODE_LOSS launch of loss kind 0 over WIDE_MIN_ROWS rows -- the launch
@@ -558,7 +449,7 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
   live.clear();
   live.reserve(nt);
   for (int32_t t = 0; t < nt; ++t)
-    if (!(P->dec.size() == (size_t)nt ? P->dec[t].static_fail : P->info[t].static_fail)) live.push_back(t);
+    if (!tree_static_fail(*P, t)) live.push_back(t);
   if (live.empty()) return SRHIP_OK;
   const size_t es = dtype_size(dtype);
   const int nl = (int)live.size();
@@ -587,14 +478,8 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
       order.insert(order.end(), goff.begin(), goff.end());  // the group offsets follow the order
       P->ord_recs = persistent ? append_slot_records(*P, order, nl, use_d) : -1;  // ... and the slot records
       if (P->upload_pending) {  // deferred program upload: program and order in one copy
-        const size_t base = P->blob_off[6], bytes = order.size() * sizeof(int32_t);
-        P->blob.resize(base + bytes);
-        memcpy(P->blob.data() + base, order.data(), bytes);
-        HIP_TRY(P->d_prog.ensure(base + bytes));
-        HIP_TRY(hipMemcpyAsync(P->d_prog.p, P->blob.data(), base + bytes, hipMemcpyHostToDevice, ctx->stream));
-        set_prog_pointers(*P);
-        P->upload_pending = false;
-        P->ord_dev = (const uint8_t*)P->d_prog.p + base;
+        const int rc = push_program_image(*P, &order, ctx->stream);
+        if (rc) return rc;
       } else {
         HIP_TRY(P->d_order.ensure(order.size() * sizeof(int32_t)));
         HIP_TRY(hipMemcpyAsync(P->d_order.p, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice,
@@ -627,7 +512,7 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
     // (every Float32 program carries its trees' +/- bounds: the interpreter folds no +/-)
     if (!P->sbound_dev || P->sbound.size() != 4 * (size_t)P->ntrees)
       return fail(SRHIP_ERR_INVALID, "Float32 program without its +/- bounds");
-    J.fbound = feature_bound(v, ds->nfeat);
+    J.fbound = feature_bound(v.stats, ds->nfeat);
   }
   a.X = v.X;
   a.y = v.y;
@@ -830,34 +715,21 @@ static int eval_collect(srhip_ctx* ctx, const srhip_program* P, const View& v, d
   ctx->last_ev1 = rs->ev1;
   ctx->timed = true;
   if (devp) {
-    const int32_t* hl = (const int32_t*)rs->h_pout.p;
-    const double* hs = (const double*)((const uint8_t*)rs->h_pout.p + PREC_SUMS_OFF);
-    dp->count = hl[0];
+    const PreciseOut out{rs->h_pout.p};
+    dp->count = out.count();
     P->und_hint = dp->count;
     const int nu = std::min(dp->count, ul.umax);
-    dp->list.assign(hl + 1, hl + 1 + nu);
-    dp->opsums.assign(hs, hs + (size_t)nu * dp->stride);
+    dp->list.assign(out.list(), out.list() + nu);
+    dp->opsums.assign(out.sums(), out.sums() + (size_t)nu * dp->stride);
   }
-  // the reduction's records, read from the device-written (coherent) host buffers in bulk copies:
-  // line-sized reads, not one uncached access per tree
-  static thread_local std::vector<uint64_t> r_loss, r_chk, r_rows;
-  r_loss.resize(nt);
-  r_chk.resize(nt);
-  r_rows.resize(nt);
-  if (mode == MODE_LOSS) memcpy(r_loss.data(), rs->h_loss.p, (size_t)nt * 8);
-  if (dtype != SRHIP_I32) memcpy(r_chk.data(), rs->h_chk.p, (size_t)nt * (dtype == SRHIP_F32 ? 4 : 8));
-  memcpy(r_rows.data(), rs->h_rows.p, (size_t)nt * 8);
+  Records rec;
+  rec.read(dtype, nt, mode == MODE_LOSS ? rs->h_loss.p : nullptr, rs->h_chk.p, rs->h_rows.p);
   for (int32_t t : live) {
     if (sd) break;  // the shard's loss sums and statistics are in the exchange's device buffer
-    if (mode == MODE_LOSS)
-      sums[2 * (size_t)t] = dtype == SRHIP_I32 ? (double)((const long long*)r_loss.data())[t] : ((const double*)r_loss.data())[t];
-    if (dtype == SRHIP_F32) {
-      const float m = ((const float*)r_chk.data())[t];
-      // a single-block launch's records come straight from the interpreter: its +/- bound applied here
-      chk[t] = J.pl.fused ? skip_bound_apply(m, P->sbound.data() + 4 * (size_t)t, J.fbound) : m;
-    } else if (dtype == SRHIP_F64) {
-      chk[t] = ((const double*)r_chk.data())[t];
-    }
+    if (mode == MODE_LOSS) sums[2 * (size_t)t] = rec.loss_sum(t);
+    // a single-block launch's records come straight from the interpreter: its +/- bound applied here
+    const bool bound = dtype == SRHIP_F32 && J.pl.fused;
+    chk[t] = bound ? skip_bound_apply((float)rec.chk_raw(t), P->sbound.data() + 4 * (size_t)t, J.fbound) : rec.chk_raw(t);
   }
   if (persistent) {
     // every row block was claimed exactly once: the workgroups' evaluated items add up to the launch's
@@ -871,15 +743,7 @@ static int eval_collect(srhip_ctx* ctx, const srhip_program* P, const View& v, d
   }
   // the launch's work, counted on the device (rows each tree was evaluated on)
   for (int i = 0; i < 4; ++i) ctx->work[i] = 0;
-  const bool pdec = P->dec.size() == (size_t)nt;
-  for (int32_t t : live) {
-    const int64_t rows = ((const int64_t*)r_rows.data())[t];
-    const int64_t nn = pdec ? P->dec[t].nnodes : P->info[t].nnodes, no = pdec ? P->dec[t].nops : P->info[t].nops;
-    ctx->work[0] += rows * nn;
-    ctx->work[1] += v.m * nn;
-    ctx->work[2] += rows * no;
-    ctx->work[3] += rows;
-  }
+  for (int32_t t : live) count_work(ctx->work, rec.rows_done(t), v.m, tree_size(*P, t));
   g_tail_done = std::chrono::steady_clock::now();
   return SRHIP_OK;
 }
@@ -958,7 +822,7 @@ int srhip::precise_decide(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_p
   std::vector<double> opsums((size_t)nu * stride);
   const int rc = eval_precise(ctx, ds, P, v, trees, nu, opsums.data(), grad);
   if (rc) return rc;
-  finalize_precise(*P, trees, nu, opsums.data(), out_ok, grad);
+  finalize_precise(*P, trees, nu, opsums.data(), stride, out_ok, grad);
   return SRHIP_OK;
 }
 
@@ -994,6 +858,58 @@ int srhip::stream_wait(srhip_ctx* ctx) {
   }
 }
 
+// SRHIP_DECIDE_SLOW=1: every decision from the TreeInfo vectors, not the compact records (read once per
+// call: the decide unit reads no environment and takes this flag)
+static bool decide_fast_on() { return !env_flag("SRHIP_DECIDE_SLOW"); }
+
+// An evaluation entry's preamble: the argument checks, the device, the view of the rows idx (all rows
+// without) and a weighted gather's weight sum
+static int open_view(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode, const srhip_loss* loss,
+                     const int64_t* idx, int64_t nidx, View& v) {
+  int rc = check_eval_args(ctx, ds, P, mode, loss);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = make_view(ctx, ds, idx, nidx, mode == MODE_LOSS, v);
+  if (rc) return rc;
+  return idx && ds->weighted && mode == MODE_LOSS ? gathered_weight_sum(ctx, ds, nidx, v) : SRHIP_OK;
+}
+
+// The precise pass a host launches (eval_precise) over the undecided trees unc, as a stage of settle: their
+// per-operator sums -- row shards: summed over the shards by reduce_host -- applied, none left undecided
+static int settle_precise(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const View& v,
+                          const double* sums, const std::function<int(double*, size_t)>* reduce_host, Verdict& V,
+                          std::vector<int32_t>& unc) {
+  const int stride = std::max(1, P->max_ops);
+  std::vector<double> opsums(unc.size() * stride);
+  int rc = eval_precise(ctx, ds, P, v, unc.data(), (int32_t)unc.size(), opsums.data());
+  if (rc) return rc;
+  if (reduce_host) {
+    rc = (*reduce_host)(opsums.data(), opsums.size());
+    if (rc) return rc;
+  }
+  V.apply_precise(*P, sums, unc.data(), (int32_t)unc.size(), opsums.data(), stride);
+  unc.clear();
+  return SRHIP_OK;
+}
+
+// Where every evaluation ends: the decision from its (possibly all-reduced) partials, then the caller's
+// stages in their order while trees are undecided -- stage(V, unc) settles trees of unc through
+// V.apply_precise and takes them off the list -- then the outputs (nullable).
+template <typename... Stage>
+static int settle(const srhip_program& P, int64_t nfeat, const double* sums, const double* chk, double* out_loss,
+                  uint8_t* out_ok, Stage&&... stage) {
+  Verdict V;
+  std::vector<int32_t> unc = V.decide(P, nfeat, sums, chk, decide_fast_on());
+  int rc = SRHIP_OK;
+  ((rc = rc || unc.empty() ? rc : stage(V, unc)), ...);
+  if (rc) return rc;
+  for (int32_t t = 0; t < P.ntrees; ++t) {
+    if (out_ok) out_ok[t] = V.ok[t];
+    if (out_loss) out_loss[t] = V.loss[t];
+  }
+  return SRHIP_OK;
+}
+
 // Single-device evaluation: partials -> decision -> precise pass for undecided trees, as two halves --
 // run_issue (arguments, view, launches) and run_complete (records, decisions, the precise passes the
 // device did not settle, outputs) -- so that srhip_eval_loss_submit can return between them.
@@ -1009,18 +925,11 @@ struct RunJob {
 };
 static int run_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode, const srhip_loss* loss,
                      const int64_t* idx, int64_t nidx, void* out_pred, RunJob& R) {
-  int rc = check_eval_args(ctx, ds, P, mode, loss);
+  const int rc = open_view(ctx, ds, P, mode, loss, idx, nidx, R.v);
   if (rc) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
   R.ds = ds;
   R.P = P;
   R.mode = mode;
-  rc = make_view(ctx, ds, idx, nidx, mode == MODE_LOSS, R.v);
-  if (rc) return rc;
-  if (idx && ds->weighted && mode == MODE_LOSS) {
-    rc = gathered_weight_sum(ctx, ds, nidx, R.v);
-    if (rc) return rc;
-  }
   const int32_t nt = P->ntrees;
   if (nt == 0) {
     R.empty = true;
@@ -1042,39 +951,27 @@ static int run_complete(srhip_ctx* ctx, RunJob& R, double* out_loss, uint8_t* ou
     rc = eval_collect(ctx, P, v, sums.data(), R.chk.data(), &dp, nullptr, R.J);
     if (rc) return rc;
   }
-  const int32_t nt = P->ntrees;
-  std::vector<uint8_t> status(nt), ok(nt);
-  std::vector<double> lossv(nt);
-  finalize(*P, ds->nfeat, sums.data(), R.chk.data(), lossv.data(), ok.data(), status.data());
-  std::vector<int32_t> unc;
-  for (int32_t t = 0; t < nt; ++t)
-    if (status[t] == 2) unc.push_back(t);
-  if (dp.used && !unc.empty()) {
-    // undecided trees the device's precise pass already covered (every undecided tree is listed by
-    // the device: its test is the host's minus the host-only checks, so the list is a superset)
+  // undecided trees the device's precise pass already covered (every undecided tree is listed by
+  // the device: its test is the host's minus the host-only checks, so the list is a superset)
+  const auto device_list = [&](Verdict& V, std::vector<int32_t>& unc) -> int {
     std::vector<int32_t> rest;
     for (int32_t t : unc) {
-      const auto it = std::find(dp.list.begin(), dp.list.end(), t);
-      if (it == dp.list.end()) {
-        rest.push_back(t);
-        continue;
-      }
-      const size_t u = (size_t)(it - dp.list.begin());
-      uint8_t uok = 0;
-      finalize_precise(*P, &t, 1, dp.opsums.data() + u * dp.stride, &uok);
-      ok[t] = uok;
-      lossv[t] = uok ? sums[2 * (size_t)t] / sums[2 * (size_t)t + 1] : INFINITY;
+      const auto it = dp.used ? std::find(dp.list.begin(), dp.list.end(), t) : dp.list.end();
+      if (it == dp.list.end()) rest.push_back(t);
+      else V.apply_precise(*P, sums.data(), &t, 1, dp.opsums.data() + (size_t)(it - dp.list.begin()) * dp.stride, dp.stride);
     }
     unc.swap(rest);
-  }
+    return SRHIP_OK;
+  };
   // trees past the device list's capacity (a program's first evaluation lists at most 4): the same
   // device-listed pass over a host-written list, DEV_PRECISE_MAX trees at a time -- every undecided
   // tree of a device evaluation is then settled by one summation path (SRHIP_PRECISE_OVERFLOW_HOST=1:
   // the host-launched pass of eval_precise instead).  (A submitted evaluation reaches this after the
   // work queued behind it; its view is the whole dataset -- submits of row subsets complete at once --
   // and its results land in its own result set.)
-  ResultSet* const rs = R.J.rs;
-  if (dp.used && !unc.empty() && !env_flag("SRHIP_PRECISE_OVERFLOW_HOST")) {
+  const auto overflow_batches = [&](Verdict& V, std::vector<int32_t>& unc) -> int {
+    if (!dp.used || env_flag("SRHIP_PRECISE_OVERFLOW_HOST")) return SRHIP_OK;
+    const PreciseOut out{R.J.rs->h_pout.p};
     const size_t bcap = (size_t)precise_cap(P, v, DEV_PRECISE_MAX);
     for (size_t b = 0; b < unc.size(); b += bcap) {
       const int32_t n = (int32_t)std::min<size_t>(bcap, unc.size() - b);
@@ -1084,41 +981,20 @@ static int run_complete(srhip_ctx* ctx, RunJob& R, double* out_loss, uint8_t* ou
       HIP_TRY(hipMemcpyAsync(ctx->d_ulist.p, lst.data(), lst.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                              ctx->stream));
       int stride = 1;
-      rc = enqueue_dev_precise(ctx, ds, P, v, (int32_t*)ctx->d_ulist.p, n, n, &stride, rs);
+      int rc = enqueue_dev_precise(ctx, ds, P, v, (int32_t*)ctx->d_ulist.p, n, n, &stride, R.J.rs);
       if (rc) return rc;
       rc = stream_wait(ctx);
       if (rc) return rc;
-      const int32_t* hl = (const int32_t*)rs->h_pout.p;
-      const double* hs = (const double*)((const uint8_t*)rs->h_pout.p + PREC_SUMS_OFF);
-      if (hl[0] != n) return fail(SRHIP_ERR_DEVICE, "precise pass listed %d of %d trees", (int)hl[0], (int)n);
-      for (int32_t u = 0; u < n; ++u) {
-        const int32_t t = hl[1 + u];
-        uint8_t uok = 0;
-        finalize_precise(*P, &t, 1, hs + (size_t)u * stride, &uok);
-        ok[t] = uok;
-        lossv[t] = uok ? sums[2 * (size_t)t] / sums[2 * (size_t)t + 1] : INFINITY;
-      }
+      if (out.count() != n) return fail(SRHIP_ERR_DEVICE, "precise pass listed %d of %d trees", (int)out.count(), (int)n);
+      V.apply_precise(*P, sums.data(), out.list(), n, out.sums(), stride);
     }
     unc.clear();
-  }
-  if (!unc.empty()) {
-    const int stride = std::max(1, P->max_ops);
-    std::vector<double> opsums(unc.size() * stride);
-    rc = eval_precise(ctx, ds, P, v, unc.data(), (int32_t)unc.size(), opsums.data());
-    if (rc) return rc;
-    std::vector<uint8_t> uok(unc.size());
-    finalize_precise(*P, unc.data(), (int32_t)unc.size(), opsums.data(), uok.data());
-    for (size_t u = 0; u < unc.size(); ++u) {
-      const int32_t t = unc[u];
-      ok[t] = uok[u];
-      lossv[t] = uok[u] ? sums[2 * (size_t)t] / sums[2 * (size_t)t + 1] : INFINITY;
-    }
-  }
-  for (int32_t t = 0; t < nt; ++t) {
-    if (out_ok) out_ok[t] = ok[t];
-    if (out_loss) out_loss[t] = lossv[t];
-  }
-  return SRHIP_OK;
+    return SRHIP_OK;
+  };
+  const auto host_pass = [&](Verdict& V, std::vector<int32_t>& unc) -> int {
+    return settle_precise(ctx, ds, P, v, sums.data(), nullptr, V, unc);
+  };
+  return settle(*P, ds->nfeat, sums.data(), R.chk.data(), out_loss, out_ok, device_list, overflow_batches, host_pass);
 }
 
 int srhip::run_eval(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode, const srhip_loss* loss,
@@ -1169,16 +1045,9 @@ int srhip::run_eval(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program
 // (srhip_comm.cpp: RCCL on the device); nfeat is the dataset's feature count on every rank.
 int srhip::run_eval_sharded(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
                             const int64_t* idx, int64_t nidx, const ShardIO& io, double* out_loss, uint8_t* out_ok) {
-  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
   View v;
-  rc = make_view(ctx, ds, idx, nidx, true, v);
+  int rc = open_view(ctx, ds, P, MODE_LOSS, loss, idx, nidx, v);
   if (rc) return rc;
-  if (idx && ds->weighted) {
-    rc = gathered_weight_sum(ctx, ds, nidx, v);
-    if (rc) return rc;
-  }
   const int32_t nt = P->ntrees;
   if (nt == 0) return SRHIP_OK;
   const int64_t nf = ds->nfeat;
@@ -1216,35 +1085,12 @@ int srhip::run_eval_sharded(srhip_ctx* ctx, const srhip_dataset* ds, const srhip
   // (this shard's persistent launch was checked to have evaluated every row block by eval_collect,
   // from its own item count -- not from the all-reduced statistic, which another shard's failures can
   // make non-finite: ADVICE r05)
-  std::vector<uint8_t> status(nt), ok(nt);
-  std::vector<double> lossv(nt);
-  finalize(*P, nf, sums.data(), chk.data(), lossv.data(), ok.data(), status.data());
-  std::vector<int32_t> unc;
-  for (int32_t t = 0; t < nt; ++t)
-    if (status[t] == 2) unc.push_back(t);
   // every rank took the same decision from the same reduced partials: the undecided set agrees, and so
   // does whether the second exchange happens.  (The single-device path lists undecided trees on the
   // device; here the list depends on the all-reduced statistic, which the host already holds.)
-  if (!unc.empty()) {
-    const int stride = std::max(1, P->max_ops);
-    std::vector<double> opsums(unc.size() * stride);
-    rc = eval_precise(ctx, ds, P, v, unc.data(), (int32_t)unc.size(), opsums.data());
-    if (rc) return rc;
-    rc = io.reduce_host(opsums.data(), opsums.size());
-    if (rc) return rc;
-    std::vector<uint8_t> uok(unc.size());
-    finalize_precise(*P, unc.data(), (int32_t)unc.size(), opsums.data(), uok.data());
-    for (size_t u = 0; u < unc.size(); ++u) {
-      const int32_t t = unc[u];
-      ok[t] = uok[u];
-      lossv[t] = uok[u] ? sums[2 * (size_t)t] / sums[2 * (size_t)t + 1] : INFINITY;
-    }
-  }
-  for (int32_t t = 0; t < nt; ++t) {
-    if (out_ok) out_ok[t] = ok[t];
-    if (out_loss) out_loss[t] = lossv[t];
-  }
-  return SRHIP_OK;
+  return settle(*P, nf, sums.data(), chk.data(), out_loss, out_ok, [&](Verdict& V, std::vector<int32_t>& unc) {
+    return settle_precise(ctx, ds, P, v, sums.data(), &io.reduce_host, V, unc);
+  });
 }
 
 // The launch order a fresh Float32 program's first large evaluation will use (eval_partials'
@@ -1258,7 +1104,7 @@ static void plan_persistent_order(const srhip_ctx* ctx, srhip_program& P) {
   std::vector<int32_t> live;
   live.reserve(P.ntrees);
   for (int32_t t = 0; t < P.ntrees; ++t)
-    if (!P.info[t].static_fail) live.push_back(t);
+    if (!tree_static_fail(P, t)) live.push_back(t);
   if (live.empty()) return;
   const int nl = (int)live.size();
   const EvalPlan pl = plan_eval(plan_input(ctx, P, nl));
@@ -1611,7 +1457,6 @@ static int eval_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pro
   const int dtype = P->dtype;
   const int64_t nf = ds->nfeat;
   const bool weighted = ds->weighted;
-  const bool pdec = P->dec.size() == (size_t)nt;
   if (dtype == SRHIP_F32 && (P->sbound.size() != 4 * (size_t)nt))
     return fail(SRHIP_ERR_INVALID, "Float32 program without its +/- bounds");
   // the sets a wave can stage go into the launch, longest and costliest first; the others run alone
@@ -1619,7 +1464,7 @@ static int eval_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pro
   std::vector<int32_t> live, alone;
   int64_t longest = 0;
   for (int32_t t = 0; t < nt; ++t) {
-    if (pdec ? P->dec[t].static_fail : P->info[t].static_fail) continue;  // decided without a launch
+    if (tree_static_fail(*P, t)) continue;  // decided without a launch
     const int64_t m = row_offsets[t + 1] - row_offsets[t];
     if (m > cap) {
       alone.push_back(t);
@@ -1635,7 +1480,8 @@ static int eval_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pro
   ResultSet* const rs = &ctx->rs[0];
   const FeatStat* fstat = nullptr;
   const double* wsum = nullptr;  // the mean's denominator of a weighted dataset
-  static thread_local std::vector<uint64_t> r_loss, r_chk, r_rows, r_fs;
+  static thread_local std::vector<uint64_t> r_fs;
+  Records rec;
   if (nl > 0) {
     const int ld_lds = (int)((longest + tile - 1) / tile * tile);
     const int cpb = std::max(1, (ld_lds + loss_chunk(dtype) - 1) / loss_chunk(dtype));
@@ -1649,10 +1495,8 @@ static int eval_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pro
     HIP_TRY(hipMemcpyAsync(ctx->vidx.p, up.data(), up.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     if (P->upload_pending) {  // the coalescer's deferred program image: uploaded here, no cached order survives
       std::lock_guard<std::mutex> g(P->ord_mu);
-      HIP_TRY(P->d_prog.ensure(P->blob_off[6]));
-      HIP_TRY(hipMemcpyAsync(P->d_prog.p, P->blob.data(), P->blob_off[6], hipMemcpyHostToDevice, ctx->stream));
-      set_prog_pointers(*P);
-      P->upload_pending = false;
+      rc = push_program_image(*P, nullptr, ctx->stream);
+      if (rc) return rc;
       P->ord_key[0] = P->ord_key[1] = P->ord_key[2] = -1;
       P->ord_goff.clear();
     }
@@ -1709,13 +1553,8 @@ static int eval_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pro
     rc = stream_wait(ctx);  // the call's one synchronisation
     if (rc) return rc;
     // the records, out of the device-written (coherent) buffers in bulk copies
-    r_loss.resize(nt);
-    r_chk.resize(nt);
-    r_rows.resize(nt);
+    rec.read(dtype, nt, rs->h_loss.p, rs->h_chk.p, rs->h_rows.p);
     r_fs.resize(rs_bytes / 8);
-    memcpy(r_loss.data(), rs->h_loss.p, (size_t)nt * 8);
-    if (dtype != SRHIP_I32) memcpy(r_chk.data(), rs->h_chk.p, (size_t)nt * (dtype == SRHIP_F32 ? 4 : 8));
-    memcpy(r_rows.data(), rs->h_rows.p, (size_t)nt * 8);
     memcpy(r_fs.data(), ctx->h_rowsets.p, r_fs.size() * 8);
     fstat = (const FeatStat*)r_fs.data();
     wsum = weighted ? (const double*)((const uint8_t*)r_fs.data() + fs_bytes) + (e ? nt : 0) : nullptr;
@@ -1724,33 +1563,18 @@ static int eval_rowsets(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pro
   int64_t work[4] = {0, 0, 0, 0};
   std::vector<double> sums(sums_len(nt, nf), 0.0);
   std::vector<int32_t> undecided;
-  const bool fast = pdec && !env_flag("SRHIP_DECIDE_SLOW");
+  const bool fast = decide_fast_on();
   for (int32_t t = 0; t < nt; ++t) {  // statically failing trees, and defaults
     out_loss[t] = INFINITY;
     out_ok[t] = 0;
   }
   for (int32_t t : live) {
     const int64_t m = row_offsets[t + 1] - row_offsets[t];
-    View v{};
-    v.m = m;
-    v.stats = fstat + (size_t)t * nf;
-    fill_decide_inputs(sums.data(), nt, nf, dtype == SRHIP_I32 ? nullptr : v.stats, m);  // (Int32 data: zeros)
-    double chk = 0.0;
-    if (dtype == SRHIP_F32)
-      chk = skip_bound_apply(((const float*)r_chk.data())[t], P->sbound.data() + 4 * (size_t)t, feature_bound(v, nf));
-    else if (dtype == SRHIP_F64)
-      chk = ((const double*)r_chk.data())[t];
-    const double lsum = dtype == SRHIP_I32 ? (double)((const long long*)r_loss.data())[t] : ((const double*)r_loss.data())[t];
-    const int st = fast ? decide_fast(*P, t, nf, sums.data(), chk) : decide_info(P->info[t], dtype, nt, nf, sums.data(), chk);
+    const int st = decide_rowset(*P, t, nf, m, fstat + (size_t)t * nf, rec.chk_raw(t), fast, sums.data());
     if (st == 2) undecided.push_back(t);
     out_ok[t] = st == 0 ? 1 : 0;
-    out_loss[t] = st == 0 ? lsum / (weighted ? wsum[t] : (double)m) : INFINITY;
-    const int64_t done = ((const int64_t*)r_rows.data())[t];
-    const int64_t nn = pdec ? P->dec[t].nnodes : P->info[t].nnodes, no = pdec ? P->dec[t].nops : P->info[t].nops;
-    work[0] += done * nn;
-    work[1] += m * nn;
-    work[2] += done * no;
-    work[3] += done;
+    out_loss[t] = verdict_loss(st == 0, rec.loss_sum(t), weighted ? wsum[t] : (double)m);
+    count_work(work, rec.rows_done(t), m, tree_size(*P, t));
   }
   alone.insert(alone.end(), undecided.begin(), undecided.end());
   for (int32_t t : alone) {
@@ -1939,16 +1763,9 @@ int srhip_eval_loss_batch(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_n
 int srhip_eval_loss_partials(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
                              const int64_t* idx, int64_t nidx, double* sums, double* chk) {
   if (!sums || !chk) return fail(SRHIP_ERR_INVALID, "null output");
-  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
-  if (rc) return rc;
-  HIP_TRY(hipSetDevice(ctx->device));
   View v;
-  rc = make_view(ctx, ds, idx, nidx, true, v);
+  const int rc = open_view(ctx, ds, P, MODE_LOSS, loss, idx, nidx, v);
   if (rc) return rc;
-  if (idx && ds->weighted) {
-    rc = gathered_weight_sum(ctx, ds, nidx, v);
-    if (rc) return rc;
-  }
   return eval_partials(ctx, ds, P, MODE_LOSS, loss, v, nullptr, sums, chk);
 }
 
@@ -1959,7 +1776,7 @@ int srhip_partials_finalize(const srhip_program* P, int64_t nfeatures, const dou
   for (const TreeInfo& I : P->info)
     for (int f : I.feat_checks)
       if (f >= nfeatures) return fail(SRHIP_ERR_INVALID, "tree checks feature %d of %lld", f + 1, (long long)nfeatures);
-  finalize(*P, nfeatures, sums, chk, out_loss, out_ok, out_status);
+  finalize(*P, nfeatures, sums, chk, decide_fast_on(), out_loss, out_ok, out_status);
   return SRHIP_OK;
 }
 
@@ -1982,7 +1799,24 @@ int srhip_precise_finalize(const srhip_program* P, const int32_t* trees, int32_t
   if (!P || !opsums || !out_ok || (!trees && ntrees_sel > 0)) return fail(SRHIP_ERR_INVALID, "null argument");
   for (int32_t u = 0; u < ntrees_sel; ++u)
     if (trees[u] < 0 || trees[u] >= P->ntrees) return fail(SRHIP_ERR_INVALID, "tree index %d out of range", trees[u]);
-  finalize_precise(*P, trees, ntrees_sel, opsums, out_ok);
+  finalize_precise(*P, trees, ntrees_sel, opsums, std::max(1, P->max_ops), out_ok);
+  return SRHIP_OK;
+}
+
+int srhip_decide_rowset(const srhip_program* P, int32_t tree, int64_t nfeatures, int64_t rows, const double* feat_stats,
+                        double chk_raw, uint8_t* out_status, double* out_chk) {
+  if (!P || !out_status || (!feat_stats && nfeatures > 0)) return fail(SRHIP_ERR_INVALID, "null argument");
+  if (tree < 0 || tree >= P->ntrees) return fail(SRHIP_ERR_INVALID, "tree index %d out of range", tree);
+  if (nfeatures < 0 || rows < 1) return fail(SRHIP_ERR_INVALID, "nfeatures < 0 or rows < 1");
+  for (int f : P->info[tree].feat_checks)
+    if (f >= nfeatures) return fail(SRHIP_ERR_INVALID, "tree checks feature %d of %lld", f + 1, (long long)nfeatures);
+  if (P->dtype == SRHIP_F32 && P->sbound.size() != 4 * (size_t)P->ntrees)
+    return fail(SRHIP_ERR_INVALID, "Float32 program without its +/- bounds");
+  std::vector<FeatStat> st((size_t)nfeatures);
+  for (int64_t f = 0; f < nfeatures; ++f)
+    st[f] = FeatStat{feat_stats[3 * f], feat_stats[3 * f + 1] > 0.0 ? 1 : 0, feat_stats[3 * f + 2]};
+  std::vector<double> sums(sums_len(P->ntrees, nfeatures), 0.0);
+  *out_status = (uint8_t)decide_rowset(*P, tree, nfeatures, rows, st.data(), chk_raw, decide_fast_on(), sums.data(), out_chk);
   return SRHIP_OK;
 }
 

@@ -2,7 +2,8 @@
 // (srhip_host.cpp: program upload, datasets, evaluation driver, C ABI; srhip_compile.cpp: the tree
 // compiler, device-free; srhip_plan.cpp: the launch decision and the launch order, device-free;
 // srhip_optim.cpp: constant gradients and the batched BFGS constant optimizer, whose state machine is
-// srhip_bfgs.cpp, device-free with a header of its own).  Not part of the public ABI.
+// srhip_bfgs.cpp, device-free with a header of its own; srhip_decide.cpp: the did_succeed decision,
+// device-free, srhip_decide.h).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -58,13 +59,6 @@ inline bool early_exit_on() {
   } while (0)
 
 inline size_t dtype_size(int dtype) { return dtype == SRHIP_F64 ? 8 : 4; }
-
-// overflow thresholds of an exact sum rounded to T: 2^128 - 2^103 and 2^1024 - 2^970
-// (computed once: an ldexpl call per use cost ~1 us per 25 trees in the host decisions)
-inline long double ovf_threshold(int dtype) {
-  static const long double f64 = ldexpl(1.0L, 1024) - ldexpl(1.0L, 970), f32 = ldexpl(1.0L, 128) - ldexpl(1.0L, 103);
-  return dtype == SRHIP_F64 ? f64 : f32;
-}
 
 // ---------------------------------------------------------------------------------------------
 // device buffers
@@ -357,9 +351,6 @@ struct View {
 int upload_program(srhip_program& P, bool sync = true, bool defer = false, hipStream_t stream = nullptr);
 int make_view(srhip_ctx* ctx, const srhip_dataset* ds, const int64_t* idx, int64_t nidx, bool need_y, View& v);
 int gathered_weight_sum(srhip_ctx* ctx, const srhip_dataset* ds, int64_t nidx, View& v);
-// did_succeed decision of tree t from partials in the srhip_eval_loss_partials layout:
-// 0 ok, 1 fail, 2 undecided (only the sums' feature / row-count entries are read)
-int decide_tree(const TreeInfo& I, const srhip_program& P, int64_t nfeat, const double* sums, double chk);
 // the context's failed-tree marks for one early-exit launch over n trees / chunks: a fresh epoch
 // (> 0) that no stale mark can equal; the marks are zeroed on the stream when (re)allocated
 int next_fail_epoch(srhip_ctx* ctx, int64_t n, int32_t** flags, int32_t* epoch);
@@ -441,18 +432,6 @@ inline void set_consts(srhip_node* nd, int64_t i, const double*& c) {
 int subprogram(srhip_ctx* ctx, const srhip_program* P, const std::vector<int32_t>& trees, srhip_program** Q);
 // The row-set entry points' conventions and error texts: offsets from 0, no empty set, rows in range.
 int check_rowsets(const srhip_dataset* ds, int32_t nt, const int64_t* row_offsets, const int64_t* rows);
-// The partials layout decide_tree reads (srhip_host.cpp "the did_succeed decision"): its length, and the
-// decision inputs of one view or row set written into it -- (sum, non-finite count) per feature (zeros
-// without stats: Int32 data), then the row count.  The per-tree entries in front are left alone.
-inline size_t sums_len(int32_t ntrees, int64_t nfeat) { return 2 * (size_t)ntrees + 2 * (size_t)nfeat + 1; }
-inline void fill_decide_inputs(double* sums, int32_t ntrees, int64_t nfeat, const FeatStat* stats, int64_t rows) {
-  double* const tail = sums + 2 * (size_t)ntrees;
-  for (int64_t f = 0; f < nfeat; ++f) {
-    tail[2 * f] = stats ? stats[f].sum : 0.0;
-    tail[2 * f + 1] = stats ? (double)stats[f].nonfinite : 0.0;
-  }
-  tail[2 * nfeat] = (double)rows;
-}
 int run_eval_sharded(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss,
                      const int64_t* idx, int64_t nidx, const ShardIO& io, double* out_loss, uint8_t* out_ok);
 

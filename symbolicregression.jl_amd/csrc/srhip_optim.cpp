@@ -34,6 +34,7 @@
 #include "srhip_grad.h"
 #include "srhip_grad_lossx.h"
 #include "srhip_internal.h"
+#include "srhip_decide.h"
 
 using namespace srhip;
 

@@ -131,6 +131,7 @@ SIGNATURES = {
     "srhip_partials_finalize": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "srhip_eval_precise_partials": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp]),
     "srhip_precise_finalize": (ctypes.c_int, [_vp, _vp, _i32, _vp, _vp]),
+    "srhip_decide_rowset": (ctypes.c_int, [_vp, _i32, _i64, _i64, _vp, ctypes.c_double, _vp, _vp]),
     "srhip_chk_reduce_op": (ctypes.c_int, [ctypes.c_int]),
     "srhip_program_max_ops": (_i32, [_vp]),
     "srhip_eval_loss_grad": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, _vp, _vp, _vp]),

@@ -40,14 +40,14 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_device_free_units_call_no_hip_runtime():
-    """The tree compiler, the launch decision and the constant optimiser's state machine
-    (csrc/srhip_compile.cpp, csrc/srhip_plan.cpp, csrc/srhip_bfgs.cpp) are host arithmetic: their objects
-    have no undefined symbol of the HIP runtime API (hipMalloc, hipMemcpyAsync, ...).  The library's own
-    srhip:: helpers (fail, last_error, env_get, ...) are expected."""
+    """The tree compiler, the launch decision, the constant optimiser's state machine and the did_succeed
+    decision (csrc/srhip_compile.cpp, csrc/srhip_plan.cpp, csrc/srhip_bfgs.cpp, csrc/srhip_decide.cpp) are host
+    arithmetic: their objects have no undefined symbol of the HIP runtime API (hipMalloc, hipMemcpyAsync, ...).
+    The library's own srhip:: helpers (fail, last_error, env_get, ...) are expected."""
     import srhip._lib as L
 
     build = os.path.dirname(L.LIB_PATH)
-    for unit in ("srhip_compile", "srhip_plan", "srhip_bfgs"):
+    for unit in ("srhip_compile", "srhip_plan", "srhip_bfgs", "srhip_decide"):
         obj = os.path.join(build, unit + ".o")
         assert os.path.isfile(obj), f"{obj} is missing: the build makes it"
         out = subprocess.run(["nm", "-u", obj], capture_output=True, text=True, check=True).stdout

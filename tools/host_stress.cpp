@@ -1,7 +1,7 @@
 // host_stress.cpp — concurrency / memory stress of libsrhip's host C++ through the C ABI, the driver the
 // sanitizer builds run (SURVEY.md 5 sanitizers row; the reference's CI runs --check-bounds=yes,
 // .github/workflows/CI.yml:72).  `make -C tools asan` / `make -C tools tsan` link it against a libsrhip
-// whose host objects (srhip_host.cpp, srhip_compile.cpp, srhip_plan.cpp, srhip_batch.cpp, srhip_optim.cpp,
+// whose host objects (srhip_host.cpp, srhip_compile.cpp, srhip_plan.cpp, srhip_decide.cpp, srhip_batch.cpp, srhip_optim.cpp,
 // srhip_comm.cpp) are built with
 // -fsanitize=address,undefined / -fsanitize=thread (on the host side only: -Xarch_host), the sanitizer
 // runtime linked into this executable -- no LD_PRELOAD.
@@ -9,7 +9,8 @@
 // Host phase (no GPU needed): THREADS threads compile host-only programs (ctx = NULL) of random
 // populations at once (srhip_compile.cpp) -- the persistent host pool, the 64-shard code cache with its first-sighting
 // table (populations recur, so trees are cached on their second sighting and hit from their third),
-// background teardown -- query and set constants, run srhip_partials_finalize over random partials,
+// background teardown -- query and set constants, run srhip_partials_finalize, srhip_precise_finalize and
+// srhip_decide_rowset over random partials,
 // and feed malformed node tables (bad children, bad operator indices) that must fail cleanly.
 // Device phase (only when a device is visible): concurrent clients of the cross-population coalescer
 // (srhip_batcher: per-request completion, two worker contexts), submitted evaluations waited out of
@@ -142,6 +143,25 @@ static void host_worker(int id, int rounds, const std::vector<Population>* pops)
     for (int64_t f = 0; f < nf; ++f) sums[2 * (size_t)nt + 2 * f] = 1.0;
     sums[2 * (size_t)nt + 2 * nf] = 4096.0;
     CHECK(srhip_partials_finalize(P, nf, sums.data(), chk.data(), loss.data(), ok.data(), status.data()));
+    // the precise pass's verdict over random per-operator sums of every tree, and the row-set form of the
+    // decision per tree over random set statistics (non-finite and near-threshold values among them)
+    const int32_t stride = srhip_program_max_ops(P);
+    std::vector<int32_t> sel(nt);
+    for (int32_t t = 0; t < nt; ++t) sel[t] = t;
+    std::vector<double> opsums((size_t)nt * stride);
+    for (double& s : opsums) s = (rng() % 40 == 0) ? NAN : std::ldexp((rng() % 2) ? 1.0 : -1.0, (int)(rng() % 130));
+    CHECK(srhip_precise_finalize(P, sel.data(), nt, opsums.data(), ok.data()));
+    std::vector<double> fst(3 * (size_t)nf);
+    for (int32_t t = 0; t < nt; ++t) {
+      for (int64_t f = 0; f < nf; ++f) {
+        fst[3 * f] = std::ldexp(1.0, (int)(rng() % 130));
+        fst[3 * f + 1] = (rng() % 30 == 0) ? 1.0 : 0.0;
+        fst[3 * f + 2] = (rng() % 30 == 0) ? INFINITY : std::ldexp(1.0, (int)(rng() % 128));
+      }
+      double applied = 0.0;
+      const double raw = chk[t] > 3.0e38 ? INFINITY : chk[t];  // (a Float32 statistic)
+      CHECK(srhip_decide_rowset(P, t, nf, 1 + (int64_t)(rng() % 5000), fst.data(), raw, &status[t], &applied));
+    }
     srhip_program_destroy(P);  // (background teardown)
     // the launch decision over random shapes (srhip_plan_eval: arithmetic on sizes, no device)
     srhip_plan_query q{};
