@@ -243,6 +243,46 @@ int srhip_eval_loss_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pr
                          double* out_loss, uint8_t* out_ok);
 /* Rows of one block of the loss pass's summation (a compile-time constant of the library). */
 int32_t srhip_lossx_block_rows(void);
+/* srhip_eval_loss_expr in ONE launch: the interpreter's prediction mode with the loss program
+ * behind it in the same kernel, the predictions in a scratch bounded by the launch geometry
+ * (srhip_plan_eval_lossx), never ntrees * m.  out_loss / out_ok have exactly the bits of srhip_eval_loss_expr
+ * (the same summation order, the same did_succeed decision); argument errors are its own.  There is no
+ * residency cap: SRHIP_LOSSX_MAX_BYTES is not read.  srhip_last_kernel_ms reports the fused launch and its
+ * finishing sum, srhip_last_work what the launch counted (no tree exits early in prediction mode). */
+int srhip_eval_loss_expr_fused(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog,
+                               const srhip_loss_expr* e, const int64_t* idx, int64_t nidx,
+                               double* out_loss, uint8_t* out_ok);
+/* srhip_eval_loss_submit under a loss expression: the fused launch queued on the context's stream, completed
+ * by srhip_eval_loss_wait with the bits of srhip_eval_loss_expr.  The ticket is the same type and counts with
+ * the built-in tickets towards the 3 a context may have outstanding; any wait order.  A row subset is
+ * evaluated inside the call.  Program, dataset and expression must outlive the ticket. */
+int srhip_eval_loss_expr_submit(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog,
+                                const srhip_loss_expr* e, const int64_t* idx, int64_t nidx,
+                                srhip_eval_ticket** out_ticket);
+/* The fused launch's geometry, for tests, from shapes and device limits alone.  No device is
+ * needed.  rb_rows: rows of an item's row block, a multiple of srhip_lossx_block_rows(); xlds: the block's
+ * feature columns are staged in LDS (lds_cols bytes of them fit lds_budget), else read from global memory;
+ * tpg trees per item, ngroups tree groups, nblocks row blocks; wgs workgroups, at most wg_per_cu per CU (the
+ * workgroups resident at the kernel's register need: 1) and one per item; scratch_bytes = wgs * tpg * rb_rows * sizeof(T): the predictions' scratch.  Returns 0, or a
+ * negative value for arguments out of range (null pointers, nlive < 0, m <= 0, maxfeat < 0, num_cu <= 0,
+ * lds_max <= 0, a dtype other than SRHIP_F32 / SRHIP_F64). */
+typedef struct srhip_lossx_plan_query {
+  int32_t dtype;
+  int32_t nlive;   /* trees not failed statically */
+  int32_t maxfeat; /* staged feature columns */
+  int32_t num_cu;
+  int64_t m;       /* rows */
+  int64_t lds_max; /* the device's LDS bytes per workgroup */
+} srhip_lossx_plan_query;
+typedef struct srhip_lossx_plan_info {
+  int32_t rb_rows, R, xlds, tpg, ngroups, wgs, wg_per_cu, pad;
+  int64_t nblocks;
+  int64_t lds;           /* dynamic LDS bytes of a workgroup */
+  int64_t lds_cols;      /* bytes of the block's feature columns */
+  int64_t lds_budget;    /* what a workgroup may stage */
+  int64_t scratch_bytes;
+} srhip_lossx_plan_info;
+int srhip_plan_eval_lossx(const srhip_lossx_plan_query* q, srhip_lossx_plan_info* out);
 
 /* Convenience: program_create + eval_loss + program_destroy. */
 int srhip_eval_loss_batch(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_node* nodes,
@@ -627,6 +667,14 @@ typedef struct srhip_batcher srhip_batcher;
 int srhip_batcher_create(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_operators* ops,
                          const srhip_loss* loss, int32_t max_batch, int32_t max_wait_us,
                          srhip_batcher** out);
+/* The same coalescer under a loss given as an expression: a flush is one program plus ONE fused launch
+ * (srhip_eval_loss_expr_fused), its subset group one srhip_eval_loss_expr_rowsets launch.  A request's result
+ * has the bits of srhip_eval_loss_expr on that tree alone.  The dataset must suit the expression (dtype,
+ * nargs against its weights: srhip_eval_loss_expr's errors, reported here); the expression must outlive the
+ * batcher.  Every other srhip_batcher_* entry is unchanged. */
+int srhip_batcher_create_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_operators* ops,
+                              const srhip_loss_expr* e, int32_t max_batch, int32_t max_wait_us,
+                              srhip_batcher** out);
 /* expected number of concurrent clients (0 = unknown: flush on max_batch / max_wait_us only) */
 int srhip_batcher_set_clients(srhip_batcher* b, int32_t nclients);
 /* one tree (nodes[0] is its root); idx = optional 0-based row subset (copied) */

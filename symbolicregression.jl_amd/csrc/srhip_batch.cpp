@@ -71,6 +71,7 @@ struct srhip_batcher {
   const srhip_dataset* ds = nullptr;
   std::vector<int32_t> binops, unaops;
   srhip_loss loss{};
+  const srhip_loss_expr* expr = nullptr;  // srhip_batcher_create_expr: the loss of every flush (the caller's)
   int32_t max_batch = 256;
   int32_t max_wait_us = 200;
   int32_t nclients = 0;
@@ -107,6 +108,10 @@ int run_slot_program(srhip_batcher* b, Worker& w, std::vector<srhip_node>&& node
   if (rc) return rc;
   rc = upload_program(P, false, true);  // uploaded with the launch's tree order, one copy
   if (rc) return rc;
+  if (b->expr) {  // a loss expression: the row-set launch, or the one-launch form over the whole dataset
+    if (rows) return srhip_eval_loss_expr_rowsets(w.ctx, b->ds, &P, b->expr, row_offs->data(), rows->data(), loss, ok);
+    return srhip_eval_loss_expr_fused(w.ctx, b->ds, &P, b->expr, nullptr, 0, loss, ok);
+  }
   if (rows) return srhip_eval_loss_rowsets(w.ctx, b->ds, &P, &b->loss, row_offs->data(), rows->data(), loss, ok);
   return srhip_eval_loss(w.ctx, b->ds, &P, &b->loss, nullptr, 0, loss, ok);
 }
@@ -221,10 +226,9 @@ void srhip_batcher::run(Worker& w) {
   }
 }
 
-extern "C" {
-
-int srhip_batcher_create(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_operators* ops, const srhip_loss* loss,
-                         int32_t max_batch, int32_t max_wait_us, srhip_batcher** out) {
+// the two creates: a built-in loss (nullable: L2), or a loss expression
+static int batcher_create(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_operators* ops, const srhip_loss* loss,
+                          const srhip_loss_expr* expr, int32_t max_batch, int32_t max_wait_us, srhip_batcher** out) {
   if (!ctx || !ds || !ops || !out) return fail(SRHIP_ERR_INVALID, "null argument");
   if (max_batch < 1 || max_wait_us < 0) return fail(SRHIP_ERR_INVALID, "max_batch >= 1 and max_wait_us >= 0 required");
   if ((ops->nbin > 0 && !ops->binops) || (ops->nuna > 0 && !ops->unaops) || ops->nbin < 0 || ops->nuna < 0)
@@ -235,6 +239,7 @@ int srhip_batcher_create(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_op
   b->binops.assign(ops->binops, ops->binops + ops->nbin);
   b->unaops.assign(ops->unaops, ops->unaops + ops->nuna);
   if (loss) b->loss = *loss;
+  b->expr = expr;
   b->max_batch = max_batch;
   b->max_wait_us = max_wait_us;
   static const int nworkers_env = [] { const char* e = getenv("SRHIP_COALESCE_WORKERS"); return e ? atoi(e) : 0; }();
@@ -280,6 +285,23 @@ int srhip_batcher_create(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_op
   }
   *out = b;
   return SRHIP_OK;
+}
+
+extern "C" {
+
+int srhip_batcher_create(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_operators* ops, const srhip_loss* loss,
+                         int32_t max_batch, int32_t max_wait_us, srhip_batcher** out) {
+  return batcher_create(ctx, ds, ops, loss, nullptr, max_batch, max_wait_us, out);
+}
+
+int srhip_batcher_create_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_operators* ops, const srhip_loss_expr* e,
+                              int32_t max_batch, int32_t max_wait_us, srhip_batcher** out) {
+  if (!ctx || !ds || !ops || !out) return fail(SRHIP_ERR_INVALID, "null argument");
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  // what every flush would be refused for, reported once here: a flush's program has the dataset's dtype
+  const int rc = check_loss_expr_data(ds, ds->dtype, e);
+  if (rc) return rc;
+  return batcher_create(ctx, ds, ops, nullptr, e, max_batch, max_wait_us, out);
 }
 
 int srhip_batcher_set_clients(srhip_batcher* b, int32_t nclients) {

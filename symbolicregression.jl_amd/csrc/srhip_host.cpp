@@ -284,9 +284,15 @@ int srhip::check_loss_expr_args(srhip_ctx* ctx, const srhip_dataset* ds, const s
   if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
   const int rc = check_eval_args(ctx, ds, P, MODE_PRED, nullptr);
   if (rc) return rc;
-  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "loss expressions are Float32 / Float64 only (Int32 program)");
-  if (P->dtype != e->prog.dtype)
-    return fail(SRHIP_ERR_INVALID, "loss expression dtype %d != program dtype %d", e->prog.dtype, P->dtype);
+  return check_loss_expr_data(ds, P->dtype, e);
+}
+
+int srhip::check_loss_expr_data(const srhip_dataset* ds, int dtype, const srhip_loss_expr* e) {
+  if (!ds) return fail(SRHIP_ERR_INVALID, "null handle");
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  if (dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "loss expressions are Float32 / Float64 only (Int32 program)");
+  if (dtype != e->prog.dtype)
+    return fail(SRHIP_ERR_INVALID, "loss expression dtype %d != program dtype %d", e->prog.dtype, dtype);
   if (!ds->has_y) return fail(SRHIP_ERR_INVALID, "dataset has no y");
   if (ds->weighted != (e->prog.nargs == 3))
     return fail(SRHIP_ERR_INVALID, "a%s dataset needs a loss expression of nargs = %d (this one has nargs = %d)",
@@ -412,6 +418,12 @@ struct EvalJob {
   UndecidedList ul;
   DevBuf pred;  // MODE_PRED's device output (synchronous calls only)
   float fbound = 0.0f;  // Float32: the features' max |x| (feature_bound: the +/- bound's F)
+  // the one-launch form of a loss expression (eval_issue_lossx; mode is MODE_PRED): the loss program, the
+  // launch's order (tree of each slot: the result set's h_loss holds the loss sums by slot, then the weights'
+  // sum), and the order's upload [order | identity | prog_off by slot] with its device copy
+  const LossxProgram* lx = nullptr;
+  std::vector<int32_t> lx_order, lx_tail;
+  PoolBuf lx_dev;
 };
 
 // What plan_eval reads of a context and a program with nlive live trees (in EvalPlanIn's order): an
@@ -422,6 +434,161 @@ static EvalPlanIn plan_input(const srhip_ctx* ctx, const srhip_program& P, int32
   return EvalPlanIn{P.dtype, MODE_LOSS, nlive, WIDE_MIN_ROWS, P.maxfeat, (int32_t)P.dspec.size(), P.kmax, P.dkmax,
                     has_wide_ops(P.unaops), /*weighted*/ false, /*sharded*/ false, /*have_recs*/ true,
                     /*loss_kind*/ 0, ctx->num_cu, ctx->lds_max};
+}
+
+// What follows an evaluation's interpreter launch on the stream, for every launch form: the undecided list's
+// set-up, the Float32 +/- bounds, the per-tree reduction of the launch's slabs into the result set's records
+// (r.run: a fused single-block launch has written them itself) and the device-listed precise pass.
+struct ReduceIn {
+  bool run;
+  const void* slab_loss;
+  int nch, cpb;
+  const void* slab_chk;
+  int nrb, nslots;
+  const int32_t* order;
+  void* out_loss;
+  void* out_chk;
+  const int32_t* slab_rows;
+  bool chk_inf;
+  int32_t* items_done;
+  int64_t* out_items;
+};
+static int issue_records(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const View& v, DevPrecise* dp,
+                         EvalJob& J, bool devp, int ucap, const ReduceIn& r) {
+  ResultSet* const rs = J.rs;
+  UndecidedList& ul = J.ul;
+  int ul_groups = 4;
+  if (devp) {
+    if (!ctx->d_ulist.p) {
+      // [count, DEV_PRECISE_MAX trees, the precise reduction's finished-workgroup counter]
+      HIP_TRY(ctx->d_ulist.ensure((2 + DEV_PRECISE_MAX) * sizeof(int32_t)));
+      HIP_TRY(hipMemsetAsync(ctx->d_ulist.p, 0, ctx->d_ulist.bytes, ctx->stream));
+    }
+    ul.ulist = (int32_t*)ctx->d_ulist.p;
+    // trees past the list's capacity are settled by the same pass over a host-written list (run_eval).
+    // The precise launch's workgroups per row block: the program's last count plus two (4 at least)
+    ul.umax = ucap;
+    ul.rows = (double)v.m;
+    ul_groups = std::min(ul.umax, std::max(4, P->und_hint + 2));
+  }
+  if (P->dtype == SRHIP_F32) {  // the reduction raises each tree's statistic to its +/- bound
+    ul.sbound = P->sbound_dev;
+    ul.fbound = J.fbound;
+  }
+  if (r.run)
+    HIP_TRY(launch_reduce(P->dtype, r.slab_loss, r.nch, r.cpb, r.slab_chk, r.nrb, r.nslots, r.order, r.out_loss, r.out_chk,
+                          ctx->stream, r.slab_rows, (int64_t*)rs->h_rows.p, ul, r.chk_inf, r.items_done, r.out_items));
+  if (devp) {
+    int stride = 1;
+    const int rc = enqueue_dev_precise(ctx, ds, P, v, ul.ulist, ul.umax, ul_groups, &stride, rs);
+    if (rc) return rc;
+    dp->used = true;
+    dp->stride = stride;
+  }
+  return SRHIP_OK;
+}
+
+// eval_issue for a loss expression in one launch (J.lx; srhip_eval_lossx.hip): the fused launch and its
+// finishing sums, then what a MODE_PRED grid launch is followed by -- the reduction of the check statistics and
+// rows evaluated into the result set's records, the device-listed precise pass -- so eval_collect and
+// run_complete's settle read them as they read srhip_eval_predict's.
+static int eval_issue_lossx(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const View& v, DevPrecise* dp,
+                            EvalJob& J) {
+  const int dtype = P->dtype;
+  const int32_t nt = P->ntrees;
+  ResultSet* const rs = J.rs;
+  const int nl = (int)J.live.size();
+  const bool weighted = ds->weighted;
+  const LossxPlan lp = plan_eval_lossx(LossxPlanIn{dtype, nl, v.m, P->maxfeat, ctx->num_cu, ctx->lds_max});
+  if (lp.nblocks > 0x7fffffffLL / std::max(1, lp.ngroups) || (int64_t)nl * lp.nblocks > 0x7fffffffLL)
+    return fail(SRHIP_ERR_INVALID, "loss expression: %d trees x %lld row blocks is more than one launch indexes", nl,
+                (long long)lp.nblocks);
+  const int nblocks = (int)lp.nblocks;
+  // what eval_collect reads of a plan: a grid launch whose reduction wrote the records
+  J.pl = EvalPlan{};
+  J.pl.kind = PLAN_GRID;
+  J.pl.R = lp.R;
+  J.pl.K = K_MAX;
+  J.pl.L = LaunchPlan{lp.rb_rows, nblocks, lp.ngroups, lp.tpg, lp.xlds, lp.lds};
+  // one group in descending cost: an item's trees cost alike, and the costliest items are dealt first
+  J.lx_order = make_order(*P, J.live, std::vector<int32_t>{0, nl}, false);
+  std::vector<int32_t>& tail = J.lx_tail;  // lives in the job: its copy is asynchronous
+  tail.assign(J.lx_order.begin(), J.lx_order.end());
+  tail.resize(3 * (size_t)nl);
+  for (int sl = 0; sl < nl; ++sl) {
+    tail[(size_t)nl + sl] = sl;
+    tail[2 * (size_t)nl + sl] = P->prog_off[J.lx_order[sl]];
+  }
+  const int32_t* d_tail;
+  {
+    std::lock_guard<std::mutex> g(P->ord_mu);
+    if (P->upload_pending) {  // deferred program upload (the coalescer's per-flush program): one copy
+      const int rc = push_program_image(*P, &tail, ctx->stream);
+      if (rc) return rc;
+      d_tail = (const int32_t*)P->ord_dev;
+      P->ord_key[0] = -1;  // what ord_dev holds is no plan_eval order
+    } else {
+      HIP_TRY(J.lx_dev.ensure(tail.size() * sizeof(int32_t)));
+      HIP_TRY(hipMemcpyAsync(J.lx_dev.p, tail.data(), tail.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+      d_tail = (const int32_t*)J.lx_dev.p;
+    }
+  }
+  const int nslots = nl + (weighted ? 1 : 0);
+  HIP_TRY(ctx->slab_chk.ensure((size_t)nl * nblocks * 8));
+  HIP_TRY(ctx->slab_rows.ensure((size_t)nl * nblocks * sizeof(int32_t)));
+  HIP_TRY(ctx->lossx_pred.ensure(lp.scratch_bytes));
+  HIP_TRY(ctx->lossx_part.ensure((size_t)nslots * nblocks * sizeof(double)));
+  HIP_TRY(rs->h_loss.ensure((size_t)(nt + 1) * 8, hipHostMallocCoherent));  // by slot, then the weights' sum
+  HIP_TRY(rs->h_chk.ensure((size_t)nt * 8, hipHostMallocCoherent));
+  HIP_TRY(rs->h_rows.ensure((size_t)(nt + 1) * 8, hipHostMallocCoherent));
+  if (dtype == SRHIP_F32) {
+    if (!P->sbound_dev || P->sbound.size() != 4 * (size_t)P->ntrees)
+      return fail(SRHIP_ERR_INVALID, "Float32 program without its +/- bounds");
+    J.fbound = feature_bound(v.stats, ds->nfeat);
+  }
+  EvalLossxArgs q{};
+  EvalArgs& a = q.e;
+  a.code = P->code_dev;
+  a.prog_off = d_tail + 2 * (size_t)nl;
+  a.order = d_tail + nl;
+  a.X = v.X;
+  a.slab_chk = ctx->slab_chk.p;
+  a.slab_rows = (int32_t*)ctx->slab_rows.p;
+  a.ld = v.ld;
+  a.nvalid = v.m;
+  a.ntrees = nl;
+  a.nfeat = P->maxfeat;
+  a.rb_rows = lp.rb_rows;
+  a.nrb = nblocks;
+  a.trees_per_group = lp.tpg;
+  a.max_steps = P->max_len;
+  q.lx = *J.lx;
+  q.y = v.y;
+  q.w = weighted ? v.w : nullptr;
+  q.pred = ctx->lossx_pred.p;
+  q.partials = (double*)ctx->lossx_part.p;
+  q.m = v.m;
+  q.nblocks = nblocks;
+  q.ngroups = lp.ngroups;
+  const bool devp = dp && !env_flag("SRHIP_NO_DEVICE_PRECISE");
+  int ucap = std::max(1, std::min(DEV_PRECISE_MAX, env_int("SRHIP_PRECISE_LIST", DEV_PRECISE_MAX)));
+  if (devp) {
+    const int rc = ensure_dev_precise(ctx, P, v, &ucap, rs);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipEventRecord(rs->ev0, ctx->stream));
+  HIP_TRY(launch_eval_lossx(dtype, q, lp.xlds, lp.wgs, lp.lds, (double*)rs->h_loss.p, ctx->stream));
+  HIP_TRY(hipEventRecord(rs->ev1, ctx->stream));
+  J.launched = true;
+  J.devp = devp;
+  {
+    const int rc = issue_records(ctx, ds, P, v, dp, J, devp, ucap,
+                                 ReduceIn{true, nullptr, 0, 0, ctx->slab_chk.p, nblocks, nl, d_tail, nullptr, rs->h_chk.p,
+                                          a.slab_rows, false, nullptr, nullptr});
+    if (rc) return rc;
+  }
+  HIP_TRY(hipEventRecord(rs->done, ctx->stream));
+  return SRHIP_OK;
 }
 
 static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode, const srhip_loss* loss,
@@ -451,6 +618,7 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
   for (int32_t t = 0; t < nt; ++t)
     if (!tree_static_fail(*P, t)) live.push_back(t);
   if (live.empty()) return SRHIP_OK;
+  if (J.lx) return eval_issue_lossx(ctx, ds, P, v, dp, J);
   const size_t es = dtype_size(dtype);
   const int nl = (int)live.size();
   // how the launch runs (srhip_plan.h): from here on the plan is only read
@@ -660,39 +828,16 @@ static int eval_issue(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_progr
       }
     }
   }
-  UndecidedList& ul = J.ul;
-  int ul_groups = 4;
-  if (devp) {
-    if (!ctx->d_ulist.p) {
-      // [count, DEV_PRECISE_MAX trees, the precise reduction's finished-workgroup counter]
-      HIP_TRY(ctx->d_ulist.ensure((2 + DEV_PRECISE_MAX) * sizeof(int32_t)));
-      HIP_TRY(hipMemsetAsync(ctx->d_ulist.p, 0, ctx->d_ulist.bytes, ctx->stream));
-    }
-    ul.ulist = (int32_t*)ctx->d_ulist.p;
-    // trees past the list's capacity are settled by the same pass over a host-written list (run_eval).
-    // The precise launch's workgroups per row block: the program's last count plus two (4 at least)
-    ul.umax = ucap;
-    ul.rows = (double)v.m;
-    ul_groups = std::min(ul.umax, std::max(4, P->und_hint + 2));
-  }
-  if (dtype == SRHIP_F32) {  // the reduction raises each tree's statistic to its +/- bound
-    ul.sbound = P->sbound_dev;
-    ul.fbound = J.fbound;
-  }
-  if (!a.fused)
-    HIP_TRY(launch_reduce(dtype, mode == MODE_LOSS ? ctx->slab_loss.p : nullptr, nch, cpb,
-                          dtype == SRHIP_I32 ? nullptr : ctx->slab_chk.p, L.nrb, nl, (const int32_t*)d_order,
-                          mode == MODE_LOSS ? (sd ? sd->d_loss : rs->h_loss.p) : nullptr,
-                          dtype == SRHIP_I32 ? nullptr : (sd ? sd->d_chk : rs->h_chk.p), ctx->stream, a.slab_rows,
-                          (int64_t*)rs->h_rows.p, ul, sd != nullptr,
-                          persistent ? (int32_t*)ctx->block_ctr.p + 1 : nullptr,
-                          persistent ? (int64_t*)rs->h_rows.p + nt : nullptr));
-  if (devp) {
-    int stride = 1;
-    const int rc = enqueue_dev_precise(ctx, ds, P, v, ul.ulist, ul.umax, ul_groups, &stride, rs);
+  {
+    const int rc = issue_records(
+        ctx, ds, P, v, dp, J, devp, ucap,
+        ReduceIn{!a.fused, mode == MODE_LOSS ? ctx->slab_loss.p : nullptr, nch, cpb,
+                 dtype == SRHIP_I32 ? nullptr : ctx->slab_chk.p, L.nrb, nl, (const int32_t*)d_order,
+                 mode == MODE_LOSS ? (sd ? sd->d_loss : rs->h_loss.p) : nullptr,
+                 dtype == SRHIP_I32 ? nullptr : (sd ? sd->d_chk : rs->h_chk.p), a.slab_rows, sd != nullptr,
+                 persistent ? (int32_t*)ctx->block_ctr.p + 1 : nullptr,
+                 persistent ? (int64_t*)rs->h_rows.p + nt : nullptr});
     if (rc) return rc;
-    dp->used = true;
-    dp->stride = stride;
   }
   // (no host output asked for: srhip_eval_loss_expr reads the predictions where they are, J.pred)
   if (mode == MODE_PRED && out_pred)
@@ -994,7 +1139,25 @@ static int run_complete(srhip_ctx* ctx, RunJob& R, double* out_loss, uint8_t* ou
   const auto host_pass = [&](Verdict& V, std::vector<int32_t>& unc) -> int {
     return settle_precise(ctx, ds, P, v, sums.data(), nullptr, V, unc);
   };
-  return settle(*P, ds->nfeat, sums.data(), R.chk.data(), out_loss, out_ok, device_list, overflow_batches, host_pass);
+  if (!R.J.lx)
+    return settle(*P, ds->nfeat, sums.data(), R.chk.data(), out_loss, out_ok, device_list, overflow_batches, host_pass);
+  // a loss expression in one launch: srhip_eval_predict's decision, then each succeeded tree's loss from its
+  // slot's sum -- the finishing kernel left them in the result set -- as srhip_eval_loss_expr divides it
+  std::vector<uint8_t> ok(P->ntrees, 0);
+  rc = settle(*P, ds->nfeat, sums.data(), R.chk.data(), nullptr, ok.data(), device_list, overflow_batches, host_pass);
+  if (rc) return rc;
+  const int32_t nl = (int32_t)R.J.lx_order.size();
+  const double* hs = R.J.launched ? (const double*)R.J.rs->h_loss.p : nullptr;
+  for (int32_t t = 0; t < P->ntrees; ++t) {
+    if (out_loss) out_loss[t] = INFINITY;
+    if (out_ok) out_ok[t] = ok[t];
+  }
+  if (out_loss && hs) {
+    const double den = ds->weighted ? hs[nl] : (double)v.m;
+    for (int32_t sl = 0; sl < nl; ++sl)
+      if (ok[R.J.lx_order[sl]]) out_loss[R.J.lx_order[sl]] = hs[sl] / den;
+  }
+  return SRHIP_OK;
 }
 
 int srhip::run_eval(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, int mode, const srhip_loss* loss,
@@ -1629,8 +1792,9 @@ struct srhip_eval_ticket {
   std::vector<uint8_t> ok;
 };
 
-int srhip_eval_loss_submit(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog, const srhip_loss* loss,
-                           const int64_t* idx, int64_t nidx, srhip_eval_ticket** out) {
+// the two submits: a built-in loss, or (e) a loss expression in its one-launch form
+static int submit_eval(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog, const srhip_loss* loss,
+                       const srhip_loss_expr* e, const int64_t* idx, int64_t nidx, srhip_eval_ticket** out) {
   if (!out) return fail(SRHIP_ERR_INVALID, "null ticket output");
   *out = nullptr;
   if (!ctx || !prog) return fail(SRHIP_ERR_INVALID, "null argument");
@@ -1640,7 +1804,8 @@ int srhip_eval_loss_submit(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_
     // a row subset's gather synchronises the stream and its buffers are the context's: evaluated here
     t->loss.resize(prog->ntrees);
     t->ok.resize(prog->ntrees);
-    const int rc = run_eval(ctx, ds, prog, MODE_LOSS, loss, idx, nidx, t->loss.data(), nullptr, t->ok.data());
+    const int rc = e ? srhip_eval_loss_expr_fused(ctx, ds, prog, e, idx, nidx, t->loss.data(), t->ok.data())
+                     : run_eval(ctx, ds, prog, MODE_LOSS, loss, idx, nidx, t->loss.data(), nullptr, t->ok.data());
     if (rc) return rc;
     t->done = true;
     *out = t.release();
@@ -1651,7 +1816,8 @@ int srhip_eval_loss_submit(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_
     if (!ctx->rs[i].busy) k = i;
   if (k < 0) return fail(SRHIP_ERR_INVALID, "%d evaluations already in flight on this context", RESULT_SETS - 1);
   t->R.J.rs = &ctx->rs[k];
-  const int rc = run_issue(ctx, ds, prog, MODE_LOSS, loss, nullptr, 0, nullptr, t->R);
+  if (e) t->R.J.lx = &e->prog;
+  const int rc = run_issue(ctx, ds, prog, e ? MODE_PRED : MODE_LOSS, loss, nullptr, 0, nullptr, t->R);
   if (rc) {
     (void)hipStreamSynchronize(ctx->stream);  // launches may have been queued before the failure
     return rc;
@@ -1659,6 +1825,19 @@ int srhip_eval_loss_submit(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_
   ctx->rs[k].busy = true;
   *out = t.release();
   return SRHIP_OK;
+}
+
+int srhip_eval_loss_submit(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog, const srhip_loss* loss,
+                           const int64_t* idx, int64_t nidx, srhip_eval_ticket** out) {
+  return submit_eval(ctx, ds, prog, loss, nullptr, idx, nidx, out);
+}
+
+int srhip_eval_loss_expr_submit(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog, const srhip_loss_expr* e,
+                                const int64_t* idx, int64_t nidx, srhip_eval_ticket** out) {
+  if (out) *out = nullptr;
+  const int rc = check_loss_expr_args(ctx, ds, prog, e);
+  if (rc) return rc;
+  return submit_eval(ctx, ds, prog, nullptr, e, idx, nidx, out);
 }
 
 int srhip_eval_loss_wait(srhip_eval_ticket* ticket, double* out_loss, uint8_t* out_ok) {
@@ -1746,6 +1925,28 @@ int srhip_eval_loss_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pr
   const double den = ds->weighted ? sums[nl] : (double)v.m;
   for (int32_t s = 0; s < nl; ++s) out_loss[live[s]] = sums[s] / den;
   return SRHIP_OK;
+}
+
+// srhip_eval_loss_expr in one launch (srhip_eval_lossx.hip): no prediction buffer, no residency cap, no host
+// round trip between the evaluation and the loss; the same decision stages, the same summation order.
+int srhip_eval_loss_expr_fused(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* prog, const srhip_loss_expr* e,
+                               const int64_t* idx, int64_t nidx, double* out_loss, uint8_t* out_ok) {
+  if (!e) return fail(SRHIP_ERR_INVALID, "null loss expression");
+  if (!out_loss || !out_ok) return fail(SRHIP_ERR_INVALID, "null output");
+  int rc = check_loss_expr_args(ctx, ds, prog, e);
+  if (rc) return rc;
+  RunJob R;
+  R.J.rs = &ctx->rs[0];
+  R.J.lx = &e->prog;
+  rc = run_issue(ctx, ds, prog, MODE_PRED, nullptr, idx, nidx, nullptr, R);
+  if (rc) return rc;
+  if (R.J.launched) {
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+  } else {
+    ctx->timed = false;  // every tree failed statically: no launch
+  }
+  return run_complete(ctx, R, out_loss, out_ok);
 }
 
 int srhip_eval_loss_batch(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_node* nodes, const int64_t* offsets,

@@ -219,6 +219,9 @@ struct srhip_ctx {
   srhip::DevBuf slab_rows;  // [row block][order slot] valid rows evaluated
   srhip::DevBuf d_ulist;    // the device's undecided-tree list ([0] = count; reset by its consumer)
   srhip::DevBuf lossx_work; // srhip_eval_loss_expr's loss pass: [block partials | per-slot sums | tree list]
+  // the one-launch form (srhip_eval_lossx.hip): the workgroups' prediction slabs, bounded by the launch geometry
+  // (plan_eval_lossx), and the block partials by order slot
+  srhip::DevBuf lossx_pred, lossx_part;
   // work of the last srhip_eval_loss / srhip_eval_predict on this context (srhip_last_work):
   // evaluated node-rows, nominal node-rows (every live tree on every row), evaluated operator-node
   // rows, evaluated tree-rows
@@ -360,6 +363,9 @@ int run_eval(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, in
 // check_eval_args for an entry point whose loss is an expression: dtype (Int32: unsupported), y, and the
 // dataset's weights against the expression's nargs
 int check_loss_expr_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const srhip_loss_expr* e);
+// ... its checks of the expression against the data and the element type of the programs to come (a program's
+// dtype is its dataset's: check_eval_args): what srhip_batcher_create_expr can check before any program exists
+int check_loss_expr_data(const srhip_dataset* ds, int dtype, const srhip_loss_expr* e);
 // The precise did_succeed pass for undecided trees (exact per-operator-node sums over the view), on the
 // evaluation program or (grad = true) on the gradient program: out_ok[u] for trees[u].
 int precise_decide(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const View& v,

@@ -231,4 +231,27 @@ int rowset_lossx_cap(int dtype, int64_t nfeat, bool weighted);
 hipError_t launch_rowsets_lossx(int dtype, const RowsetArgs& a, const LossxProgram& lx, void* pred, double* out_loss,
                                 double* out_wsum, int nlaunch, hipStream_t s);
 
+// A whole view under a loss given as an expression, in one launch (srhip_eval_lossx.hip;
+// srhip_eval_loss_expr_fused, srhip_eval_loss_expr_submit, the expression coalescer).  e is a MODE_PRED launch
+// over the plain program in the shape of ONE item: rb_rows = LOSSX_BLOCK_ROWS, uniform groups of trees_per_group
+// order slots, no y / w / loss kind, not fused, not persistent; slab_chk / slab_rows are [nblocks][ntrees] by
+// order slot, as launch_reduce reads them.  The launch relabels its trees by order slot: e.order is the
+// identity and e.prog_off is indexed by slot, so a workgroup's predictions pack into its own slab.
+struct EvalLossxArgs {
+  EvalArgs e;
+  LossxProgram lx;
+  const void* y;     // [ld] the view's targets
+  const void* w;     // [ld] its weights (weighted datasets), or nullptr
+  void* pred;        // [workgroups][trees_per_group][LOSSX_BLOCK_ROWS] T: each workgroup's predictions of its item
+  double* partials;  // [ntrees + (w ? 1 : 0)][nblocks] by order slot, then the weights' slot: lossx_kernel's partials
+  int64_t m;         // rows of the view
+  int32_t nblocks;   // loss blocks: ceil(m / LOSSX_BLOCK_ROWS)
+  int32_t ngroups;   // tree groups: ceil(ntrees / trees_per_group)
+};
+static_assert(sizeof(EvalLossxArgs) <= 4096, "kernel arguments are limited to 4 KB");
+// the launch, then the per-slot sums of the partials in ascending block order (lossx_finish_kernel's text)
+// into out[ntrees + (w ? 1 : 0)] (coherent host memory)
+hipError_t launch_eval_lossx(int dtype, const EvalLossxArgs& q, bool xlds, int wgs, size_t lds, double* out,
+                             hipStream_t s);
+
 }  // namespace srhip

@@ -189,6 +189,35 @@ EvalPlan srhip::plan_eval(const EvalPlanIn& in) {
   return p;
 }
 
+LossxPlan srhip::plan_eval_lossx(const LossxPlanIn& in) {
+  LossxPlan p{};
+  const size_t es = dtype_size(in.dtype);
+  const int32_t nl = std::max<int32_t>(1, in.nlive);
+  const int64_t m = std::max<int64_t>(1, in.m);
+  p.rb_rows = LOSSX_BLOCK_ROWS;
+  p.R = in.dtype == SRHIP_F64 ? R_F64 : R_F32;
+  const int waves = eval_waves(p.R, K_MAX);
+  p.nblocks = lossx_blocks(m);
+  // the device's LDS less 8 KB for the interpreter's static arrays, as plan_eval's one-workgroup-per-CU budget
+  p.lds_budget = (size_t)std::max<int64_t>(0, in.lds_max - 8 * 1024);
+  p.lds_cols = (size_t)std::max<int32_t>(0, in.maxfeat) * p.rb_rows * es;
+  p.xlds = p.lds_cols <= p.lds_budget;
+  p.lds = (p.xlds ? p.lds_cols : 0) + 16;
+  // two trees per wave of an item (the waves claim them costliest first, so they end within a cheap tree of
+  // each other, and a staged block serves 16 trees); one per wave while that leaves workgroups without an item
+  p.tpg = 2 * waves;
+  if (p.nblocks * ((nl + p.tpg - 1) / p.tpg) < 2 * (int64_t)in.num_cu) p.tpg = waves;
+  p.tpg = std::min<int>(p.tpg, nl);
+  p.ngroups = (nl + p.tpg - 1) / p.tpg;
+  // one workgroup per CU: at the kernel's 162-164 VGPRs in 512-thread workgroups (2 waves per SIMD) one is
+  // resident, whatever LDS it stages; a second would wait for the first to end and only add a slab
+  p.wg_per_cu = 1;
+  const int64_t items = p.nblocks * p.ngroups;
+  p.wgs = (int)std::max<int64_t>(1, std::min<int64_t>(items, (int64_t)in.num_cu * p.wg_per_cu));
+  p.scratch_bytes = (size_t)p.wgs * p.tpg * p.rb_rows * es;
+  return p;
+}
+
 // Tree groups of a launch (grid.y), as offsets into the order: the plan's uniform groups, or —
 // when the launch spans several waves of workgroups over the chip's 2-per-CU slots — the bulk in
 // g equal groups plus ~1/32 of the trees in halving tail groups (..., 32, 16, <=16).  Workgroups
@@ -273,6 +302,27 @@ int srhip::append_slot_records(const srhip_program& P, std::vector<int32_t>& ord
 }
 
 // ---- the plan as the tests see it (include/srhip.h) ------------------------------------------------
+extern "C" int srhip_plan_eval_lossx(const srhip_lossx_plan_query* q, srhip_lossx_plan_info* out) {
+  if (!q || !out || q->nlive < 0 || q->m <= 0 || q->maxfeat < 0 || q->num_cu <= 0 || q->lds_max <= 0 ||
+      (q->dtype != SRHIP_F32 && q->dtype != SRHIP_F64))
+    return -1;
+  const LossxPlan p = plan_eval_lossx(LossxPlanIn{q->dtype, q->nlive, q->m, q->maxfeat, q->num_cu, q->lds_max});
+  *out = srhip_lossx_plan_info{};
+  out->rb_rows = p.rb_rows;
+  out->R = p.R;
+  out->xlds = p.xlds;
+  out->tpg = p.tpg;
+  out->ngroups = p.ngroups;
+  out->wgs = p.wgs;
+  out->wg_per_cu = p.wg_per_cu;
+  out->nblocks = p.nblocks;
+  out->lds = (int64_t)p.lds;
+  out->lds_cols = (int64_t)p.lds_cols;
+  out->lds_budget = (int64_t)p.lds_budget;
+  out->scratch_bytes = (int64_t)p.scratch_bytes;
+  return 0;
+}
+
 extern "C" int srhip_plan_eval(const srhip_plan_query* q, srhip_plan_info* out) {
   if (!q || !out || q->nlive < 0 || q->m <= 0 || q->num_cu <= 0 || q->lds_max <= 0 || q->maxfeat < 0 || q->nd < 0 ||
       (q->dtype != SRHIP_F32 && q->dtype != SRHIP_F64 && q->dtype != SRHIP_I32) ||

@@ -54,6 +54,29 @@ struct EvalPlan {
 };
 EvalPlan plan_eval(const EvalPlanIn& in);
 
+// The one-launch form of a loss expression (srhip_eval_lossx.hip): items of (tree group, loss block) dealt to a
+// persistent-style grid.  The row block is the loss block (a block's partial is one butterfly over 256 virtual
+// threads, so it is never split); its feature columns are staged in LDS when they fit, else read from global
+// memory; the predictions' scratch is wgs x tpg x rb_rows elements whatever ntrees x m is.  plan_eval is not
+// asked: this launch has none of its forms.
+struct LossxPlanIn {
+  int dtype;        // SRHIP_F32 / SRHIP_F64
+  int32_t nlive;    // trees not failed statically
+  int64_t m;        // rows of the view
+  int32_t maxfeat;  // staged feature columns
+  int num_cu;
+  int64_t lds_max;  // the device's LDS per workgroup
+};
+struct LossxPlan {
+  int rb_rows, R;       // rows of an item; rows per lane of the interpreter variant
+  bool xlds;
+  int tpg, ngroups;     // trees per item, tree groups
+  int64_t nblocks;      // row blocks
+  int wgs, wg_per_cu;   // workgroups of the launch: at most wg_per_cu (the resident ones: 1) per CU, one per item
+  size_t lds, lds_cols, lds_budget, scratch_bytes;
+};
+LossxPlan plan_eval_lossx(const LossxPlanIn& in);
+
 // asin / acos / atanh_clip among a program's unary operators: they live only in the K_MAX variant
 bool has_wide_ops(const std::vector<int32_t>& unaops);
 std::vector<int32_t> shape_groups(const LaunchPlan& L, int32_t ntrees, int num_cu);

@@ -74,6 +74,16 @@ class PlanInfo(ctypes.Structure):  # struct srhip_plan_info
         "fused", "hot", "pad")] + [("lds", ctypes.c_int64)]
 
 
+class LossxPlanQuery(ctypes.Structure):  # struct srhip_lossx_plan_query
+    _fields_ = [(n, ctypes.c_int32) for n in ("dtype", "nlive", "maxfeat", "num_cu")] + [
+        ("m", ctypes.c_int64), ("lds_max", ctypes.c_int64)]
+
+
+class LossxPlanInfo(ctypes.Structure):  # struct srhip_lossx_plan_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("rb_rows", "R", "xlds", "tpg", "ngroups", "wgs", "wg_per_cu", "pad")] + [
+        (n, ctypes.c_int64) for n in ("nblocks", "lds", "lds_cols", "lds_budget", "scratch_bytes")]
+
+
 class BfgsQuery(ctypes.Structure):  # struct srhip_bfgs_query
     _fields_ = [("ntrees", ctypes.c_int32), ("nstarts", ctypes.c_int32), ("const_offsets", ctypes.c_void_p),
                 ("starts", ctypes.c_void_p)] + [(n, ctypes.c_int32) for n in (
@@ -123,6 +133,9 @@ SIGNATURES = {
     "srhip_loss_expr_eval_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "srhip_eval_loss_expr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "srhip_lossx_block_rows": (_i32, []),
+    "srhip_eval_loss_expr_fused": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "srhip_eval_loss_expr_submit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_vp)]),
+    "srhip_plan_eval_lossx": (ctypes.c_int, [ctypes.POINTER(LossxPlanQuery), ctypes.POINTER(LossxPlanInfo)]),
     "srhip_eval_loss_submit": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, ctypes.POINTER(_vp)]),
     "srhip_eval_loss_wait": (ctypes.c_int, [_vp, _vp, _vp]),
     "srhip_eval_loss_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, ctypes.POINTER(Operators),
@@ -153,6 +166,8 @@ SIGNATURES = {
     "srhip_rowsets_fallback_trees": (_i64, [_vp]),
     "srhip_batcher_create": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(Operators), ctypes.POINTER(Loss), _i32, _i32,
                                             ctypes.POINTER(_vp)]),
+    "srhip_batcher_create_expr": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(Operators), _vp, _i32, _i32,
+                                                 ctypes.POINTER(_vp)]),
     "srhip_batcher_set_clients": (ctypes.c_int, [_vp, _i32]),
     "srhip_batcher_submit": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, ctypes.POINTER(ctypes.c_uint64)]),
     "srhip_batcher_wait": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.POINTER(_dbl), ctypes.POINTER(ctypes.c_uint8)]),

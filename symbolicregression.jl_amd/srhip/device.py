@@ -242,13 +242,35 @@ class Program:
                                                   ptr(offsets), ptr(rows), ptr(out), ptr(ok)))
         return out, ok.astype(bool)
 
+    def eval_loss_fused(self, ds: DeviceDataset, loss, idx=None):
+        """srhip_eval_loss_expr_fused: an ExprLoss over the whole view in one launch, (loss[T], ok[T]) with the
+        bits of eval_loss(ds, loss, idx); no prediction buffer, so no SRHIP_LOSSX_MAX_BYTES cap."""
+        from .loss_expr import ExprLoss
+
+        if not isinstance(loss, ExprLoss):
+            raise TypeError("eval_loss_fused takes an ExprLoss (a built-in loss is fused by eval_loss)")
+        out = np.empty(self.ntrees, dtype=np.float64)
+        ok = np.empty(self.ntrees, dtype=np.uint8)
+        idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        check(_lib.load().srhip_eval_loss_expr_fused(self.ctx.handle, ds.handle, self.handle, loss.handle(self.dtype),
+                                                     ptr(idxa), 0 if idxa is None else len(idxa), ptr(out), ptr(ok)))
+        return out, ok.astype(bool)
+
     def eval_loss_submit(self, ds: DeviceDataset, loss, idx=None) -> "EvalTicket":
         """srhip_eval_loss_submit: the evaluation's launches queued behind whatever is in flight on the
         context; .wait() -> (loss[T], ok[T]), the same bits as eval_loss.  At most 3 outstanding per
-        context; this program and ds must stay alive until the ticket is waited."""
-        ls = loss.c_struct()
+        context; this program and ds must stay alive until the ticket is waited.  An ExprLoss goes to
+        srhip_eval_loss_expr_submit (the one-launch form; the ticket keeps the loss alive too)."""
+        from .loss_expr import ExprLoss
+
         idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
         h = ctypes.c_void_p()
+        if isinstance(loss, ExprLoss):
+            check(_lib.load().srhip_eval_loss_expr_submit(self.ctx.handle, ds.handle, self.handle,
+                                                          loss.handle(self.dtype), ptr(idxa),
+                                                          0 if idxa is None else len(idxa), ctypes.byref(h)))
+            return EvalTicket(h, self, ds, loss)
+        ls = loss.c_struct()
         check(_lib.load().srhip_eval_loss_submit(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls), ptr(idxa),
                                                  0 if idxa is None else len(idxa), ctypes.byref(h)))
         return EvalTicket(h, self, ds)
@@ -476,13 +498,20 @@ class Coalescer:
 
     def __init__(self, ctx: Context, ds: DeviceDataset, options, loss, max_batch: int = 256,
                  max_wait_us: int = 200, nclients: int = 0):
-        self.ctx, self.ds, self.options, self.loss = ctx, ds, options, loss
+        from .loss_expr import ExprLoss
+
+        self.ctx, self.ds, self.options, self.loss = ctx, ds, options, loss  # (loss: alive as long as the batcher)
         self._ops = options.c_operators()
-        self._loss = loss.c_struct()
         h = ctypes.c_void_p()
-        check(_lib.load().srhip_batcher_create(ctx.handle, ds.handle, ctypes.byref(self._ops),
-                                               ctypes.byref(self._loss), int(max_batch), int(max_wait_us),
-                                               ctypes.byref(h)))
+        if isinstance(loss, ExprLoss):  # a flush is one program and one fused launch (srhip_eval_loss_expr_fused)
+            check(_lib.load().srhip_batcher_create_expr(ctx.handle, ds.handle, ctypes.byref(self._ops),
+                                                        loss.handle(ds.dtype), int(max_batch), int(max_wait_us),
+                                                        ctypes.byref(h)))
+        else:
+            self._loss = loss.c_struct()
+            check(_lib.load().srhip_batcher_create(ctx.handle, ds.handle, ctypes.byref(self._ops),
+                                                   ctypes.byref(self._loss), int(max_batch), int(max_wait_us),
+                                                   ctypes.byref(h)))
         self.handle = h
         if nclients:
             self.set_clients(nclients)
@@ -537,8 +566,8 @@ class Coalescer:
 class EvalTicket:
     """An evaluation in flight (Program.eval_loss_submit); wait() exactly once."""
 
-    def __init__(self, handle, prog, ds):
-        self.handle, self._prog, self._ds = handle, prog, ds  # (keeps both alive until waited)
+    def __init__(self, handle, prog, ds, loss=None):
+        self.handle, self._prog, self._ds, self._loss = handle, prog, ds, loss  # (kept alive until waited)
 
     def wait(self):
         if self.handle is None:
@@ -547,5 +576,5 @@ class EvalTicket:
         ok = np.empty(self._prog.ntrees, dtype=np.uint8)
         h, self.handle = self.handle, None  # the library frees the ticket on every path
         check(_lib.load().srhip_eval_loss_wait(h, ptr(out), ptr(ok)))
-        self._prog = self._ds = None
+        self._prog = self._ds = self._loss = None
         return out, ok.astype(bool)

@@ -183,6 +183,23 @@ static void host_worker(int id, int rounds, const std::vector<Population>* pops)
       fprintf(stderr, "FAIL launch plan: kind %d nrb %d rb %d lds %lld\n", pi.kind, pi.nrb, pi.rb_rows, (long long)pi.lds);
       g_fail = 1;
     }
+    // ... and the geometry of a loss expression's one-launch form (srhip_plan_eval_lossx)
+    srhip_lossx_plan_query lq{};
+    lq.dtype = (int32_t)(rng() % 2);
+    lq.nlive = q.nlive;
+    lq.maxfeat = q.maxfeat;
+    lq.num_cu = q.num_cu;
+    lq.m = q.m;
+    lq.lds_max = q.lds_max;
+    srhip_lossx_plan_info li{};
+    if (srhip_plan_eval_lossx(&lq, &li) != 0 || li.rb_rows % srhip_lossx_block_rows() != 0 || li.tpg < 1 || li.wgs < 1 ||
+        li.wgs > lq.num_cu * li.wg_per_cu || li.wgs > li.nblocks * li.ngroups || li.lds > lq.lds_max ||
+        li.xlds != (li.lds_cols <= li.lds_budget) ||
+        li.scratch_bytes != (int64_t)li.wgs * li.tpg * li.rb_rows * (lq.dtype == SRHIP_F64 ? 8 : 4)) {
+      fprintf(stderr, "FAIL lossx plan: wgs %d tpg %d blocks %lld lds %lld\n", li.wgs, li.tpg, (long long)li.nblocks,
+              (long long)li.lds);
+      g_fail = 1;
+    }
     // malformed tables: a child index past the tree, an operator index past the table
     std::vector<srhip_node> bad(p.nodes.begin(), p.nodes.begin() + p.offs[1]);
     if (!bad.empty() && bad[0].degree > 0) {
