@@ -434,6 +434,59 @@ int srhip_optimize_constants_starts(srhip_ctx* ctx, const srhip_dataset* ds, srh
                                     double* starts_out, double* out_loss, uint8_t* out_improved,
                                     int64_t* out_fcalls);
 
+/* ---- row-sharded constant gradients and constant optimisation --------------------------
+ * ds holds THIS rank's rows (every rank the same features); every rank calls with the same program, loss,
+ * options, seed, starts_in and SRHIP_* environment.  idx indexes the rank's own rows; idx, nidx and the row
+ * count may differ between ranks.  A call opens with one exchange of the shards' totals (weight sum or rows,
+ * feature statistics, rows) and of the call's signature; if the ranks disagree on a field of it (trees, total
+ * constants, dtype, weights, loss kind and parameters, iterations, restarts, seed, g_tol, a hash of starts_in,
+ * the SRHIP_OPTIM_* knobs, a forced SRHIP_GRAD_KT) every rank returns SRHIP_ERR_INVALID naming the field.  Every
+ * evaluation after it is one exchange: the gradient kernels' shard reduction writes [loss and gradient sums |
+ * check statistics] into the communicator's device buffer, the communicator's stream waits for it through an
+ * event (no host wait), one RCCL group of at most two all-reduces (SUM; MAX for Float32 statistics), one copy to
+ * the host, one host wait.  Every rank takes the same decisions from the same reduced values.
+ *   srhip_eval_loss_grad_sharded: srhip_eval_loss_grad's outputs over all ranks' rows, identical on every
+ *     rank; with one rank it equals srhip_eval_loss_grad bit for bit.
+ *   srhip_optimize_constants_sharded: the contract of srhip_optimize_constants_starts on the objective over all
+ *     ranks' rows (baseline and re-score by srhip_eval_loss_sharded); every rank ends with the same constants in
+ *     prog.  One group on the caller's context and thread (SRHIP_OPTIM_SPLIT does not apply: a communicator
+ *     carries one exchange at a time); SRHIP_GRAD_SCREEN is ignored.  With one rank it equals
+ *     srhip_optimize_constants_starts bit for bit.
+ * Int32 programs: SRHIP_ERR_UNSUPPORTED.  A communicator with a migration in flight or on another device:
+ * SRHIP_ERR_INVALID.  Out of scope: loss expressions (there is no sharded expression scoring to re-score with),
+ * row sets, and a rank that fails locally in mid-call -- the others wait out SRHIP_COMM_TIMEOUT_S, as in
+ * srhip_eval_loss_sharded. */
+int srhip_eval_loss_grad_sharded(srhip_ctx* ctx, srhip_comm* comm, const srhip_dataset* ds, srhip_program* prog,
+                                 const srhip_loss* loss, const int64_t* idx, int64_t nidx, double* out_loss,
+                                 double* out_grad, uint8_t* out_ok);
+int srhip_optimize_constants_sharded(srhip_ctx* ctx, srhip_comm* comm, const srhip_dataset* ds,
+                                     srhip_program* prog, const srhip_loss* loss, const int64_t* idx,
+                                     int64_t nidx, const srhip_optim_options* opt, const double* starts_in,
+                                     double* starts_out, double* out_loss, uint8_t* out_improved,
+                                     int64_t* out_fcalls);
+/* The manual steps, beside srhip_eval_loss_partials, for shards combined by any transport:
+ *   1. srhip_eval_loss_grad_partials on each shard: sums[2*T + 2*F + 1] as srhip_eval_loss_partials lays them
+ *      out (the loss sums are the gradient kernels'), gsums[sum nconst] the gradient sums in get_constants
+ *      order, chk[T] the gradient program's check statistic (Float32: a non-finite one is +Inf).
+ *   2. combine: sums and gsums by SUM, chk by srhip_chk_reduce_op(dtype).
+ *   3. srhip_grad_partials_finalize (no device): out_loss[T] and out_grad[sum nconst] over the combined weight
+ *      sum, out_ok[T], out_status[T] (nullable); a failing tree is +Inf with a zero slice; status 2 =
+ *      undecided: then step 4 of the evaluation (srhip_eval_precise_partials, SUM, srhip_precise_finalize),
+ *      and a tree that fails there becomes +Inf with a zero slice.  prog is the program step 1 ran on, at the
+ *      same constants, or a host-only program (ctx = NULL) of the same trees.
+ * srhip_shard_signature_check (no device): reduced[2 * nfields] holds the MAX over the ranks of [k_i, -k_i] per
+ * field; returns the first field with max(k_i) != -max(-k_i), or -1 (-2: a null argument).  The library's own
+ * signature has srhip_shard_signature_fields() fields, named by srhip_shard_signature_field_name. */
+int srhip_eval_loss_grad_partials(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* prog,
+                                  const srhip_loss* loss, const int64_t* idx, int64_t nidx, double* sums,
+                                  double* gsums, double* chk);
+int srhip_grad_partials_finalize(srhip_program* prog, int64_t nfeatures, const double* sums,
+                                 const double* gsums, const double* chk, double* out_loss, double* out_grad,
+                                 uint8_t* out_ok, uint8_t* out_status);
+int32_t srhip_shard_signature_check(const double* reduced, int32_t nfields);
+int32_t srhip_shard_signature_fields(void);
+const char* srhip_shard_signature_field_name(int32_t field);
+
 /* srhip_eval_loss_grad with the loss given as an expression (srhip_loss_expr): the same dual-number launch
  * over (tree, constant chunk) pairs, its loss stage running the expression's program over dual numbers with
  * one tangent, d / d prediction (every operator's value and partials are the ones the trees' own operators

@@ -13,6 +13,9 @@
 //    buffer (sums by SUM, the check statistics by MAX for Float32 / SUM otherwise, issued as one
 //    RCCL group), decides did_succeed identically on every rank, and all-reduces the precise pass's
 //    per-operator sums only when some tree's overflow check is undecided.
+//    srhip_eval_loss_grad_sharded / srhip_optimize_constants_sharded do the same for the constant gradient and
+//    the constant optimiser: a call-start exchange of the shards' totals and the call's signature, then one
+//    exchange per evaluation (grad_shard_io below; the optimiser makes hundreds to thousands of them per call).
 //
 // The Julia side would obtain the communicator id on rank 0 (srhip_comm_unique_id) and broadcast its
 // 128 bytes with whatever launcher runs the ranks (MPI.jl, Distributed); INTEGRATION.md 6 shows the
@@ -38,6 +41,7 @@ struct srhip_comm {
   int nranks = 1, rank = 0;
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;
+  hipEvent_t ready = nullptr;  // recorded on a context's stream: what the exchange's stream waits for (no host wait)
   DevBuf dsend, drecv, dred;
   HostBuf hsend, hrecv, hred;
   // the migration in flight (start -> wait)
@@ -188,7 +192,8 @@ int srhip_comm_create(srhip_ctx* ctx, const uint8_t* id, int32_t nranks, int32_t
     return fail(SRHIP_ERR_DEVICE, "ncclCommInitRank: %s", ncclGetErrorString(r));
   }
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ready, hipEventDisableTiming) != hipSuccess) {
     srhip_comm_destroy(c);
     return fail(SRHIP_ERR_DEVICE, "comm stream / event creation failed");
   }
@@ -202,6 +207,7 @@ void srhip_comm_destroy(srhip_comm* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm) (void)ncclCommDestroy(c->comm);  // (an aborted communicator is already gone)
   if (c->done) (void)hipEventDestroy(c->done);
+  if (c->ready) (void)hipEventDestroy(c->ready);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -336,13 +342,39 @@ int srhip_comm_migrate_wait(srhip_comm* c, int32_t* out_counts, int64_t* out_off
   return SRHIP_OK;
 }
 
-int srhip_eval_loss_sharded(srhip_ctx* ctx, srhip_comm* c, const srhip_dataset* ds, const srhip_program* P,
-                            const srhip_loss* loss, const int64_t* idx, int64_t nidx, double* out_loss,
-                            uint8_t* out_ok) {
+}  // extern "C"
+
+namespace {
+
+// what every row-sharded entry point asks of its communicator
+int shard_comm_ok(const srhip_ctx* ctx, const srhip_comm* c) {
   if (!c) return fail(SRHIP_ERR_INVALID, "null communicator");
   if (c->pending) return fail(SRHIP_ERR_INVALID, "a migration is in flight on this communicator");
   COMM_LIVE(c);
   if (ctx && c->ctx->device != ctx->device) return fail(SRHIP_ERR_INVALID, "communicator is on another device");
+  return SRHIP_OK;
+}
+
+// f64 SUM of a host array in place, staged through the communicator's buffers
+int reduce_host_sum(srhip_comm* c, double* buf, size_t n) {
+  if (n == 0) return SRHIP_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t bytes = n * 8;
+  HIP_TRY(c->hred.ensure(bytes));
+  HIP_TRY(c->dred.ensure(bytes));
+  memcpy(c->hred.p, buf, bytes);
+  HIP_TRY(hipMemcpyAsync(c->dred.p, c->hred.p, bytes, hipMemcpyHostToDevice, c->stream));
+  NCCL_TRY(ncclAllReduce(c->dred.p, c->dred.p, n, ncclFloat64, ncclSum, c->comm, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->hred.p, c->dred.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  const int rc = comm_wait(c);
+  if (rc) return rc;
+  memcpy(buf, c->hred.p, bytes);
+  c->note(t0);
+  return SRHIP_OK;
+}
+
+// the sharded evaluation's exchanges (run_eval_sharded) on communicator c
+ShardIO eval_shard_io(srhip_comm* c) {
   // the partials never leave the device before they are reduced: the evaluation's reduction kernel writes
   // [loss | chk] into the communicator's device buffer, the host adds only the few aux values behind
   // them, and one RCCL group reduces the three segments in place on the communicator's stream (the
@@ -381,23 +413,105 @@ int srhip_eval_loss_sharded(srhip_ctx* ctx, srhip_comm* c, const srhip_dataset* 
     c->note(t0);
     return SRHIP_OK;
   };
-  io.reduce_host = [c](double* buf, size_t n) -> int {
-    if (n == 0) return SRHIP_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t bytes = n * 8;
-    HIP_TRY(c->hred.ensure(bytes));
+  io.reduce_host = [c](double* buf, size_t n) -> int { return reduce_host_sum(c, buf, n); };
+  return io;
+}
+
+// The exchanges of the row-sharded gradient and optimiser (run_grad_sharded / run_optimize_sharded).  A round:
+// the context's stream holds the gradient kernels and the shard reduction, which wrote [sums | chk] into the
+// communicator's device buffer; an event recorded there makes the communicator's stream wait -- the host does not
+// -- then one RCCL group (SUM over the sums; MAX over the check statistics of Float32, for Float64 the one SUM
+// covers both), one copy to the host, and the round's one host wait.
+GradShardIO grad_shard_io(srhip_comm* c) {
+  GradShardIO io;
+  io.buffer = [c](size_t bytes, void** d) -> int {
     HIP_TRY(c->dred.ensure(bytes));
-    memcpy(c->hred.p, buf, bytes);
-    HIP_TRY(hipMemcpyAsync(c->dred.p, c->hred.p, bytes, hipMemcpyHostToDevice, c->stream));
-    NCCL_TRY(ncclAllReduce(c->dred.p, c->dred.p, n, ncclFloat64, ncclSum, c->comm, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->hred.p, c->dred.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c->hred.ensure(bytes));
+    *d = c->dred.p;
+    return SRHIP_OK;
+  };
+  io.reduce = [c](const GradShardLayout& L, hipStream_t producer, const void** out) -> int {
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t* d = (uint8_t*)c->dred.p;
+    HIP_TRY(hipEventRecord(c->ready, producer));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->ready, 0));
+    const bool two = L.dtype == SRHIP_F32 && L.nchk > 0;
+    const size_t n1 = two ? L.nsum : L.nsum + L.nchk;
+    NCCL_TRY(ncclGroupStart());
+    ncclResult_t r1 = ncclSuccess, r2 = ncclSuccess;
+    if (n1) r1 = ncclAllReduce(d, d, n1, ncclFloat64, ncclSum, c->comm, c->stream);
+    if (r1 == ncclSuccess && two)
+      r2 = ncclAllReduce(d + L.nsum * 8, d + L.nsum * 8, L.nchk, ncclFloat64, ncclMax, c->comm, c->stream);
+    const ncclResult_t r3 = ncclGroupEnd();  // closed on every path
+    NCCL_TRY(r1);
+    NCCL_TRY(r2);
+    NCCL_TRY(r3);
+    HIP_TRY(hipMemcpyAsync(c->hred.p, d, L.bytes(), hipMemcpyDeviceToHost, c->stream));
     const int rc = comm_wait(c);
     if (rc) return rc;
-    memcpy(buf, c->hred.p, bytes);
+    *out = c->hred.p;
     c->note(t0);
     return SRHIP_OK;
   };
-  return run_eval_sharded(ctx, ds, P, loss, idx, nidx, io, out_loss, out_ok);
+  io.reduce_host = [c](double* buf, size_t n) -> int { return reduce_host_sum(c, buf, n); };
+  io.start = [c](double* sum, size_t nsum, double* mx, size_t nmax) -> int {
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t bytes = (nsum + nmax) * 8;
+    if (bytes == 0) return SRHIP_OK;
+    HIP_TRY(c->hred.ensure(bytes));
+    HIP_TRY(c->dred.ensure(bytes));
+    double* h = (double*)c->hred.p;
+    double* d = (double*)c->dred.p;
+    memcpy(h, sum, nsum * 8);
+    memcpy(h + nsum, mx, nmax * 8);
+    HIP_TRY(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
+    NCCL_TRY(ncclGroupStart());
+    ncclResult_t r1 = ncclSuccess, r2 = ncclSuccess;
+    if (nsum) r1 = ncclAllReduce(d, d, nsum, ncclFloat64, ncclSum, c->comm, c->stream);
+    if (r1 == ncclSuccess && nmax) r2 = ncclAllReduce(d + nsum, d + nsum, nmax, ncclFloat64, ncclMax, c->comm, c->stream);
+    const ncclResult_t r3 = ncclGroupEnd();
+    NCCL_TRY(r1);
+    NCCL_TRY(r2);
+    NCCL_TRY(r3);
+    HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
+    const int rc = comm_wait(c);
+    if (rc) return rc;
+    memcpy(sum, h, nsum * 8);
+    memcpy(mx, h + nsum, nmax * 8);
+    c->note(t0);
+    return SRHIP_OK;
+  };
+  return io;
+}
+
+}  // namespace
+
+extern "C" {
+
+int srhip_eval_loss_sharded(srhip_ctx* ctx, srhip_comm* c, const srhip_dataset* ds, const srhip_program* P,
+                            const srhip_loss* loss, const int64_t* idx, int64_t nidx, double* out_loss,
+                            uint8_t* out_ok) {
+  const int rc = shard_comm_ok(ctx, c);
+  if (rc) return rc;
+  return run_eval_sharded(ctx, ds, P, loss, idx, nidx, eval_shard_io(c), out_loss, out_ok);
+}
+
+int srhip_eval_loss_grad_sharded(srhip_ctx* ctx, srhip_comm* c, const srhip_dataset* ds, srhip_program* P,
+                                 const srhip_loss* loss, const int64_t* idx, int64_t nidx, double* out_loss,
+                                 double* out_grad, uint8_t* out_ok) {
+  const int rc = shard_comm_ok(ctx, c);
+  if (rc) return rc;
+  return run_grad_sharded(ctx, ds, P, loss, idx, nidx, grad_shard_io(c), out_loss, out_grad, out_ok);
+}
+
+int srhip_optimize_constants_sharded(srhip_ctx* ctx, srhip_comm* c, const srhip_dataset* ds, srhip_program* P,
+                                     const srhip_loss* loss, const int64_t* idx, int64_t nidx,
+                                     const srhip_optim_options* opt, const double* starts_in, double* starts_out,
+                                     double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
+  const int rc = shard_comm_ok(ctx, c);
+  if (rc) return rc;
+  return run_optimize_sharded(ctx, ds, P, loss, idx, nidx, opt, starts_in, starts_out, eval_shard_io(c), grad_shard_io(c),
+                              out_loss, out_improved, out_fcalls);
 }
 
 }  // extern "C"

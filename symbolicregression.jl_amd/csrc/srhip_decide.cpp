@@ -96,6 +96,37 @@ void finalize_precise(const srhip_program& P, const int32_t* trees, int32_t nsel
   }
 }
 
+void finalize_grad(const srhip_program& P, int64_t nfeat, const double* sums, const double* gsums, const double* chk,
+                   double* out_loss, double* out_grad, uint8_t* out_ok, uint8_t* out_status) {
+  size_t g0 = 0;
+  for (int32_t t = 0; t < P.ntrees; ++t) {
+    const int nc = P.info[t].nconst;
+    const int st = decide_tree(P.ginfo[t], P, nfeat, sums, chk[t]);
+    const double den = sums[2 * (size_t)t + 1];
+    if (out_status) out_status[t] = (uint8_t)st;
+    if (out_ok) out_ok[t] = st != 1;
+    if (out_loss) out_loss[t] = st == 1 ? INFINITY : sums[2 * (size_t)t] / den;
+    for (int k = 0; out_grad && k < nc; ++k) out_grad[g0 + k] = st == 1 ? 0.0 : gsums[g0 + k] / den;
+    g0 += (size_t)nc;
+  }
+}
+
+const char* shard_sig_name(int field) {
+  static const char* const names[SIG_COUNT] = {
+      "entry point", "trees", "total constants", "dtype", "weighted", "loss kind", "loss parameter 0 (high bits)",
+      "loss parameter 0 (low bits)", "loss parameter 1 (high bits)", "loss parameter 1 (low bits)", "iterations",
+      "restarts", "seed (high bits)", "seed (low bits)", "g_tol (high bits)", "g_tol (low bits)",
+      "starts_in hash (high bits)", "starts_in hash (low bits)", "SRHIP_OPTIM_VALUE_TRIALS", "SRHIP_OPTIM_SPEC",
+      "SRHIP_OPTIM_SPEC_ACTIVE", "SRHIP_OPTIM_SPEC_DEPTH", "SRHIP_GRAD_KT"};
+  return field >= 0 && field < SIG_COUNT ? names[field] : "?";
+}
+
+int shard_sig_check(const double* reduced, int nfields) {
+  for (int i = 0; i < nfields; ++i)
+    if (!(reduced[2 * i] == -reduced[2 * i + 1])) return i;  // (a NaN disagrees)
+  return -1;
+}
+
 std::vector<int32_t> Verdict::decide(const srhip_program& P, int64_t nfeat, const double* sums, const double* chk,
                                      bool fast) {
   const int32_t nt = P.ntrees;
@@ -157,3 +188,47 @@ void Records::read(int dtype, int32_t nt, const void* h_loss, const void* h_chk,
 }
 
 }  // namespace srhip
+
+using namespace srhip;
+
+extern "C" {
+
+// The gradient program's metadata must describe the program's current constants: a device program has it from
+// srhip_eval_loss_grad_partials (the step before this one); a host-only program is compiled here (no device).
+int srhip_grad_partials_finalize(srhip_program* P, int64_t nfeatures, const double* sums, const double* gsums,
+                                 const double* chk, double* out_loss, double* out_grad, uint8_t* out_ok,
+                                 uint8_t* out_status) {
+  if (!P || !sums || !chk || !out_loss || !out_grad || !out_ok) return fail(SRHIP_ERR_INVALID, "null argument");
+  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant gradients need Float32 / Float64");
+  if (nfeatures < 0) return fail(SRHIP_ERR_INVALID, "nfeatures < 0");
+  int64_t nall = 0;
+  for (int32_t t = 0; t < P->ntrees; ++t) nall += P->info[t].nconst;
+  if (!gsums && nall > 0) return fail(SRHIP_ERR_INVALID, "null gradient sums");
+  if (!P->ctx) {
+    GradEdit edit;
+    const int rc = compile_grad_host(*P, edit);
+    if (rc) return rc;
+  } else if (!P->grad_ready) {
+    return fail(SRHIP_ERR_INVALID, "the gradient program is not compiled at the program's current constants: "
+                                   "srhip_eval_loss_grad_partials comes first");
+  }
+  if (P->ginfo.size() < (size_t)P->ntrees) return fail(SRHIP_ERR_INVALID, "program without a gradient program");
+  for (int32_t t = 0; t < P->ntrees; ++t)
+    for (int f : P->ginfo[t].feat_checks)
+      if (f >= nfeatures) return fail(SRHIP_ERR_INVALID, "tree checks feature %d of %lld", f + 1, (long long)nfeatures);
+  finalize_grad(*P, nfeatures, sums, gsums, chk, out_loss, out_grad, out_ok, out_status);
+  return SRHIP_OK;
+}
+
+int32_t srhip_shard_signature_fields(void) { return (int32_t)SIG_COUNT; }
+
+const char* srhip_shard_signature_field_name(int32_t field) {
+  return field >= 0 && field < SIG_COUNT ? shard_sig_name(field) : nullptr;
+}
+
+int32_t srhip_shard_signature_check(const double* reduced, int32_t nfields) {
+  if (!reduced || nfields < 0) return -2;
+  return (int32_t)shard_sig_check(reduced, nfields);
+}
+
+}  // extern "C"

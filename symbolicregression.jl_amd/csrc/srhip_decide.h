@@ -74,6 +74,32 @@ struct Verdict {
                      int stride);
 };
 
+// ---- row-sharded constant gradients (srhip_eval_loss_grad_partials -> all-reduce -> here) ------------------
+// Loss, gradient, ok and status of every tree of P from combined partials: sums in the layout above, gsums[sum
+// nconst] the gradient sums in get_constants order, chk[T] the gradient program's check statistic.  The decision is
+// decide_tree on the gradient program's metadata (P.ginfo, which the caller has made current); loss and gradient
+// are the sums over sums[2t + 1]; a failing tree (status 1) is +Inf with a zero slice; an undecided one (status 2)
+// reports its sums' quotients and ok = 1 until the precise pass has settled it.
+void finalize_grad(const srhip_program& P, int64_t nfeat, const double* sums, const double* gsums, const double* chk,
+                   double* out_loss, double* out_grad, uint8_t* out_ok, uint8_t* out_status);
+
+// The signature of a row-sharded gradient / optimiser call: what every rank must agree on for the ranks to build
+// the same launches.  Each field is a double holding an integer below 2^53 (64-bit values travel as two halves);
+// the call-start exchange all-reduces [k_i, -k_i] by MAX, and the ranks agree on field i iff max(k_i) == -max(-k_i).
+enum ShardSigField {
+  SIG_ENTRY = 0,  // 0: srhip_eval_loss_grad_sharded, 1: srhip_optimize_constants_sharded
+  SIG_TREES, SIG_CONSTS, SIG_DTYPE, SIG_WEIGHTED, SIG_LOSS_KIND, SIG_LOSS_P0_HI, SIG_LOSS_P0_LO, SIG_LOSS_P1_HI,
+  SIG_LOSS_P1_LO, SIG_ITERATIONS, SIG_RESTARTS, SIG_SEED_HI, SIG_SEED_LO, SIG_GTOL_HI, SIG_GTOL_LO, SIG_STARTS_HI,
+  SIG_STARTS_LO, SIG_VALUE_TRIALS, SIG_SPEC_SLOTS, SIG_SPEC_ACTIVE, SIG_SPEC_DEPTH, SIG_GRAD_KT, SIG_COUNT
+};
+const char* shard_sig_name(int field);
+// reduced[2 * nfields] = the MAX-reduced [k_i, -k_i] pairs: the first field the ranks disagree on, or -1
+int shard_sig_check(const double* reduced, int nfields);
+inline void shard_sig_put64(double* k, int hi_field, uint64_t bits) {
+  k[hi_field] = (double)(uint32_t)(bits >> 32);
+  k[hi_field + 1] = (double)(uint32_t)bits;
+}
+
 // the features' max |x| over a view's or row set's rows (+Inf if any entry is non-finite, or without
 // statistics), rounded up to Float32: the F of the Float32 interpreter's +/- bound (EvalArgs::fbound)
 float feature_bound(const FeatStat* stats, int64_t nfeat);

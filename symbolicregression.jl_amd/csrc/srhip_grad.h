@@ -62,6 +62,12 @@ hipError_t launch_grad(int dtype, int K, int kt, const GradArgs& a, dim3 grid, h
 // per-row modes (GMODE_ROWC / GMODE_ROWF), GRAD_ROW_KT tangents per chunk
 hipError_t launch_grad_rows(int dtype, int K, int gmode, const GradArgs& a, dim3 grid, hipStream_t s);
 hipError_t launch_grad_reduce(int dtype, int kt, const double* slab, int nrb, int nchunks, double* out, hipStream_t s);
+// The reduction of a row shard: grad_reduce_kernel's fold (the same bits), the record of launch-order chunk c
+// written at exchange position pos[c] (nullptr: c) of a device buffer split by reduction operator --
+// sum[nchunks][kt + 1] (loss sum, gradient sums: SUM across ranks) and chk[nchunks] (the check statistic: MAX for
+// Float32, a non-finite value stored as +Inf; SUM for Float64).
+hipError_t launch_grad_reduce_shard(int dtype, int kt, const double* slab, int nrb, int nchunks, const int32_t* pos,
+                                    double* sum, double* chk, hipStream_t s);
 // derived columns of a derived view: Xd[j] = U(X[f]) over ld rows, keys[j] = U << 16 | f (nd <= 32)
 hipError_t launch_grad_derive(int dtype, const void* X, void* Xd, int64_t ld, const uint32_t* keys, int nd,
                               hipStream_t s);

@@ -144,15 +144,15 @@ void grad_kernel(GradArgs p) {
   }
 }
 
-// per-chunk fixed-order reduction over row blocks: one wave per chunk
-template <int KT, bool CHK_MAX>
-__global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restrict__ slab, int nrb, int nchunks,
-                                                          double* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (chunk >= nchunks) return;
-  // (each lane folds its row blocks b = lane, lane + 64, ... in order -- the loads of a batch issued
-  // before its adds: a strided loop waited out one memory latency per block and element)
+// per-chunk fixed-order reduction over row blocks, one wave per chunk: the fold both reduction kernels share,
+// so a row shard's record has the unsharded bits by construction.  Element e of the chunk's (KT + 2)-wide
+// record (loss sum, KT gradient sums, the check statistic -- MAX for Float32, SUM for Float64) goes to
+// write(e, value) on lane 0.
+// (each lane folds its row blocks b = lane, lane + 64, ... in order -- the loads of a batch issued
+// before its adds: a strided loop waited out one memory latency per block and element)
+template <int KT, bool CHK_MAX, class Write>
+__device__ __forceinline__ void grad_reduce_fold(const double* __restrict__ slab, int nrb, int chunk, int lane,
+                                                 Write write) {
   constexpr int BB = 8;
   for (int e = 0; e < KT + 2; ++e) {
     const bool is_max = CHK_MAX && e == KT + 1;
@@ -172,8 +172,39 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restri
       const double t = __shfl_xor(s, o);
       s = is_max ? __builtin_elementwise_maximum(s, t) : s + t;
     }
-    if (lane == 0) out[(int64_t)chunk * (KT + 2) + e] = s;
+    if (lane == 0) write(e, s);
   }
+}
+
+// ... into (KT + 2) doubles per chunk by launch position (coherent host memory)
+template <int KT, bool CHK_MAX>
+__global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restrict__ slab, int nrb, int nchunks,
+                                                          double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (chunk >= nchunks) return;
+  grad_reduce_fold<KT, CHK_MAX>(slab, nrb, chunk, lane,
+                                [&](int e, double s) { out[(int64_t)chunk * (KT + 2) + e] = s; });
+}
+
+// ... for a row shard (srhip_optim.cpp, the sharded ViewBackend): into a device buffer the ranks all-reduce in
+// place, split by reduction operator: sum[pos][KT + 1] (loss sum, gradient sums; SUM) and chk[pos] (MAX for
+// Float32, SUM for Float64).  pos[chunk] is the chunk's position in the exchange (the launch order depends on
+// the rank's row count, the exchange must not).  A non-finite Float32 statistic, NaN included, is stored as
+// +Inf, as the evaluation's shard reduction stores it (reduce_finish, srhip_eval.hip): a MAX across ranks is
+// not defined on NaN.
+template <int KT, bool CHK_MAX>
+__global__ __launch_bounds__(256) void grad_reduce_shard_kernel(const double* __restrict__ slab, int nrb, int nchunks,
+                                                                const int32_t* __restrict__ pos,
+                                                                double* __restrict__ sum, double* __restrict__ chk) {
+  const int lane = threadIdx.x & 63;
+  const int chunk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (chunk >= nchunks) return;
+  const int at = pos ? pos[chunk] : chunk;
+  grad_reduce_fold<KT, CHK_MAX>(slab, nrb, chunk, lane, [&](int e, double s) {
+    if (e <= KT) sum[(int64_t)at * (KT + 1) + e] = s;
+    else chk[at] = CHK_MAX && !__builtin_isfinite(s) ? (double)INFINITY : s;
+  });
 }
 
 // LDS staging of the row block when it fits (few features): [nfeat + 1][rb_rows] elements
@@ -295,6 +326,27 @@ hipError_t launch_grad_reduce(int dtype, int kt, const double* slab, int nrb, in
     if (kt == 4) hipLaunchKernelGGL((grad_reduce_kernel<4, false>), grid, block, 0, s, slab, nrb, nchunks, out);
     else hipLaunchKernelGGL((grad_reduce_kernel<GRAD_KT, false>), grid, block, 0, s, slab, nrb, nchunks, out);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_grad_reduce_shard(int dtype, int kt, const double* slab, int nrb, int nchunks, const int32_t* pos,
+                                    double* sum, double* chk, hipStream_t s) {
+  if (kt != 0 && kt != 4 && kt != GRAD_KT) return hipErrorInvalidValue;
+  if (dtype != SRHIP_F32 && dtype != SRHIP_F64) return hipErrorInvalidValue;
+  if (nchunks <= 0) return hipSuccess;
+  dim3 grid((nchunks + 3) / 4), block(256);
+#define SRHIP_REDUCE_SHARD(KT_, MAX_) \
+  hipLaunchKernelGGL((grad_reduce_shard_kernel<KT_, MAX_>), grid, block, 0, s, slab, nrb, nchunks, pos, sum, chk)
+  if (dtype == SRHIP_F32) {
+    if (kt == 0) SRHIP_REDUCE_SHARD(0, true);
+    else if (kt == 4) SRHIP_REDUCE_SHARD(4, true);
+    else SRHIP_REDUCE_SHARD(GRAD_KT, true);
+  } else {
+    if (kt == 0) SRHIP_REDUCE_SHARD(0, false);
+    else if (kt == 4) SRHIP_REDUCE_SHARD(4, false);
+    else SRHIP_REDUCE_SHARD(GRAD_KT, false);
+  }
+#undef SRHIP_REDUCE_SHARD
   return hipGetLastError();
 }
 

@@ -961,12 +961,17 @@ static int eval_precise(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pro
 }
 
 int srhip::precise_decide(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const View& v,
-                          const int32_t* trees, int32_t nu, bool grad, uint8_t* out_ok) {
+                          const int32_t* trees, int32_t nu, bool grad, uint8_t* out_ok,
+                          const std::function<int(double*, size_t)>* reduce_host) {
   if (nu <= 0) return SRHIP_OK;
   const int stride = std::max(1, grad ? P->gmax_ops : P->max_ops);
   std::vector<double> opsums((size_t)nu * stride);
-  const int rc = eval_precise(ctx, ds, P, v, trees, nu, opsums.data(), grad);
+  int rc = eval_precise(ctx, ds, P, v, trees, nu, opsums.data(), grad);
   if (rc) return rc;
+  if (reduce_host) {
+    rc = (*reduce_host)(opsums.data(), opsums.size());
+    if (rc) return rc;
+  }
   finalize_precise(*P, trees, nu, opsums.data(), stride, out_ok, grad);
   return SRHIP_OK;
 }

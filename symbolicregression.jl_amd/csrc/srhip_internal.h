@@ -367,9 +367,11 @@ int check_loss_expr_args(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pr
 // dtype is its dataset's: check_eval_args): what srhip_batcher_create_expr can check before any program exists
 int check_loss_expr_data(const srhip_dataset* ds, int dtype, const srhip_loss_expr* e);
 // The precise did_succeed pass for undecided trees (exact per-operator-node sums over the view), on the
-// evaluation program or (grad = true) on the gradient program: out_ok[u] for trees[u].
+// evaluation program or (grad = true) on the gradient program: out_ok[u] for trees[u].  reduce_host (row
+// shards): the view is this rank's rows, and the per-operator sums are summed over the ranks before the verdict.
 int precise_decide(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_program* P, const View& v,
-                   const int32_t* trees, int32_t nu, bool grad, uint8_t* out_ok);
+                   const int32_t* trees, int32_t nu, bool grad, uint8_t* out_ok,
+                   const std::function<int(double*, size_t)>* reduce_host = nullptr);
 
 // Row-sharded evaluation with caller-supplied exchanges (srhip_comm.cpp: RCCL).  The per-tree partials
 // stay in device memory: the evaluation's reduction kernel writes them into the exchange's own device
@@ -393,6 +395,35 @@ struct ShardIO {
   // plain f64 SUM of a host array in place (the precise pass's per-operator sums of undecided trees)
   std::function<int(double* buf, size_t n)> reduce_host;
 };
+// Row-sharded constant gradients and optimisation (srhip_optim.cpp run_grad_sharded / run_optimize_sharded;
+// the exchanges are srhip_comm.cpp's).  One evaluation of the optimiser is one exchange: the shard reduction
+// (launch_grad_reduce_shard) writes both passes' records into the exchange's device buffer, all f64,
+//   [sums of pass 0 | sums of pass 1 | chk of pass 0 | chk of pass 1]
+// (nsum then nchk doubles): the sums are all-reduced by SUM, the check statistics by MAX for Float32 and by SUM
+// for Float64 (then one all-reduce covers the buffer), and the buffer is copied to the host once.
+struct GradShardLayout {
+  int dtype = 0;
+  size_t nsum = 0, nchk = 0;
+  size_t bytes() const { return (nsum + nchk) * 8; }
+};
+struct GradShardIO {
+  // the device buffer (>= bytes) of the round, before its kernels are queued (it may reallocate)
+  std::function<int(size_t bytes, void** dptr)> buffer;
+  // the exchange's stream waits for what `producer` holds so far (an event: no host wait), the segments are
+  // all-reduced in place as one group and copied to the host; the one host wait of the round; *out: that copy
+  std::function<int(const GradShardLayout& L, hipStream_t producer, const void** out)> reduce;
+  // plain f64 SUM of a host array in place (the precise pass's per-operator sums of undecided items)
+  std::function<int(double* buf, size_t n)> reduce_host;
+  // the call-start exchange, one group: sum[nsum] by SUM and mx[nmax] by MAX, both host arrays, in place
+  std::function<int(double* sum, size_t nsum, double* mx, size_t nmax)> start;
+};
+int run_grad_sharded(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss, const int64_t* idx,
+                     int64_t nidx, const GradShardIO& gio, double* out_loss, double* out_grad, uint8_t* out_ok);
+// eio: the sharded evaluation's exchanges (run_eval_sharded), for the baseline and the final re-score
+int run_optimize_sharded(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                         const int64_t* idx, int64_t nidx, const srhip_optim_options* opt, const double* starts_in,
+                         double* starts_out, const ShardIO& eio, const GradShardIO& gio, double* out_loss,
+                         uint8_t* out_improved, int64_t* out_fcalls);
 // getenv through a per-thread cache that is dropped whenever the environment changes (srhip_host.cpp)
 const char* env_get(const char* name);
 // Wait for the context's stream: hipStreamSynchronize, or with SRHIP_SYNC_SPIN=1 a spin on a

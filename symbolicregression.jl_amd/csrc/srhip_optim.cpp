@@ -171,6 +171,21 @@ struct RowsetBatch {
 // item's tree (which names the row set where there is one).  A backend flattens it to its device list.
 struct Chunk {
   int32_t slot, c0, item, tree;
+  int32_t pos;  // its index in the pass as the items list it: the same on every rank, whatever the launch order
+};
+// One row-sharded call (srhip_eval_loss_grad_sharded / srhip_optimize_constants_sharded): its exchanges and what
+// the call-start exchange gave -- the weight sum (or row count) over all ranks, and the decision inputs over all
+// ranks' rows.  Every evaluation of the call divides by the one and decides from the other.
+struct GradShardCall {
+  const GradShardIO* io = nullptr;
+  double wsum = 0.0;
+  std::vector<double> tail;  // [per feature {column sum, non-finite count} | rows], the partials layout's tail
+};
+// What an evaluation does besides the plain one-device call (both null): a row shard's exchange, or the raw
+// records of srhip_eval_loss_grad_partials -- sums undivided, no decision, every tree's statistic to raw_chk[tree]
+struct GradExtra {
+  const GradShardCall* sh = nullptr;
+  double* raw_chk = nullptr;
 };
 // The two passes of an evaluation (gradient chunks of kt tangents, then value-only chunks: kt = 0)
 struct GradPass {
@@ -184,23 +199,53 @@ struct GradPass {
 //                           first launch (no reallocation under a queued kernel)
 //   launch(pi, ps, ev0)     the pass's chunk list and kernels on the stream, its records written to
 //                           ctx->h_gred[pi]; ev0 (nullable) recorded in front of the kernels
+//   host_records()          the launch writes its records to ctx->h_gred[pi] (false: collect() sets each pass's red)
+//   collect(pass)           the one host wait of the evaluation; every pass's red is readable after it
 //   wsum(it)                the weight sum the item's records are divided by
-//   decide_inputs(it)       the partials-layout array decide_tree reads for the item
+//   decide(it, chk)         the item's status (0 ok, 1 fail, 2 undecided) from its check statistic
 //   settle(items, und, ok)  the precise pass for the undecided items `und`: ok[u] for items[und[u]]
 
 // Every item on the view's rows (srhip_grad.hip): row blocks x chunk groups, reduced by a second kernel.
+// With a row shard's exchange (ex.sh) the view is this rank's rows: the reduction is the shard form, into the
+// exchange's device buffer; collect is the exchange (its stream waits for the kernels through an event, the host
+// waits once, for the reduced copy); the weight sum and the decision inputs are the call's global ones; settle
+// sums the precise pass's per-operator sums over the ranks before the verdict.  Every rank builds the same
+// passes -- the items are a function of the reduced values alone -- and a chunk's place in the exchange is its
+// Chunk::pos, not its place in this rank's launch order.
 struct ViewBackend {
   srhip_ctx* ctx;
   const srhip_dataset* ds;
   srhip_program* P;
   LossSel loss;  // built-in kind, or an expression program
   const View& v;
+  GradExtra ex = {};
   LaunchPlan L[2] = {};
   std::vector<double> sums;  // decision inputs: only the feature statistics and the row count are read
+  // a row shard's round: the exchange's device buffer, each pass's segments in it (in doubles), and the
+  // reduced records put back into (kt + 2) doubles per chunk by launch position
+  double* xbuf = nullptr;
+  GradShardLayout xl;
+  size_t sum_off[2] = {0, 0}, chk_off[2] = {0, 0};
+  std::vector<double> xred[2];
 
   int prepare(GradPass (&pass)[2]) {
     sums.assign(sums_len(P->ntrees, ds->nfeat), 0.0);
-    fill_decide_inputs(sums.data(), P->ntrees, ds->nfeat, v.stats, v.m);
+    if (ex.sh) std::copy(ex.sh->tail.begin(), ex.sh->tail.end(), sums.begin() + 2 * (size_t)P->ntrees);
+    else fill_decide_inputs(sums.data(), P->ntrees, ds->nfeat, v.stats, v.m);
+    if (ex.sh) {
+      const size_t n0 = pass[0].chunks.size(), n1 = pass[1].chunks.size();
+      sum_off[0] = 0;
+      sum_off[1] = n0 * (pass[0].kt + 1);
+      xl.dtype = P->dtype;
+      xl.nsum = sum_off[1] + n1 * (pass[1].kt + 1);
+      chk_off[0] = xl.nsum;
+      chk_off[1] = xl.nsum + n0;
+      xl.nchk = n0 + n1;
+      void* d = nullptr;
+      const int rc = ex.sh->io->buffer(xl.bytes(), &d);
+      if (rc) return rc;
+      xbuf = (double*)d;
+    }
     size_t slab_n = 0, red_n = 0, chunk_n = 0;
     for (int pi = 0; pi < 2; ++pi) {
       GradPass& ps = pass[pi];
@@ -229,11 +274,11 @@ struct ViewBackend {
       }
       slab_n = std::max(slab_n, (size_t)nch * L[pi].nrb * (ps.kt + 2));
       red_n = std::max(red_n, (size_t)nch * (ps.kt + 2));
-      chunk_n = std::max(chunk_n, (size_t)2 * nch);
+      chunk_n = std::max(chunk_n, (size_t)(ex.sh ? 3 : 2) * nch);  // (a shard: the exchange positions behind the list)
     }
     HIP_TRY(ctx->g_chunks.ensure(chunk_n * sizeof(int32_t)));
     HIP_TRY(ctx->g_slab.ensure(slab_n * sizeof(double)));
-    HIP_TRY(ctx->g_red.ensure(red_n * sizeof(double)));
+    if (!ex.sh) HIP_TRY(ctx->g_red.ensure(red_n * sizeof(double)));  // (a shard's records go to the exchange's buffer)
     return SRHIP_OK;
   }
 
@@ -246,16 +291,18 @@ struct ViewBackend {
     GradArgs a{};
     // SRHIP_GRAD_INLINE_MAX (0: always copy the list), read per pass through the environment cache
     // so a test can compare both forms in one process
-    const bool inl = nch <= std::max(0, std::min(env_int("SRHIP_GRAD_INLINE_MAX", GRAD_INLINE), GRAD_INLINE));
+    // (a shard always copies: its list carries every chunk's exchange position behind the (slot, c0) pairs)
+    const bool inl = !ex.sh && nch <= std::max(0, std::min(env_int("SRHIP_GRAD_INLINE_MAX", GRAD_INLINE), GRAD_INLINE));
     // the device list, (slot, c0) per chunk: in the kernel arguments, or through pinned staging (a pageable
     // source makes the runtime stage the copy through its own buffer, synchronously); stream order: the
     // copy follows the previous pass's kernel, which has read its chunk list
-    const size_t list_bytes = (size_t)2 * nch * sizeof(int32_t);
+    const size_t list_bytes = (size_t)(ex.sh ? 3 : 2) * nch * sizeof(int32_t);
     if (!inl) HIP_TRY(ctx->h_gchunks[pi].ensure(list_bytes));
     int32_t* const list = inl ? a.inl : (int32_t*)ctx->h_gchunks[pi].p;
     for (int c = 0; c < nch; ++c) {
       list[2 * c] = ps.chunks[c].slot;
       list[2 * c + 1] = ps.chunks[c].c0;
+      if (ex.sh) list[2 * nch + c] = ps.chunks[c].pos;
     }
     if (!inl) HIP_TRY(hipMemcpyAsync(ctx->g_chunks.p, list, list_bytes, hipMemcpyHostToDevice, ctx->stream));
     a.code = (const Ins*)P->d_gcode.p;
@@ -290,7 +337,8 @@ struct ViewBackend {
     // (test_value_only_screening_is_exact).  C4 (~40 % of its trial points overflow), same box:
     // off 173.6-177.9 ms, every pass 190-193, passes of >= 16 chunks 176.8-179.6 -- the extra launch
     // costs what the skipped blocks save at 100k rows.
-    const int screen_min = env_int("SRHIP_GRAD_SCREEN", 0);
+    // (ignored on a row shard: which chunks a rank screens out depends on its own rows)
+    const int screen_min = ex.sh ? 0 : env_int("SRHIP_GRAD_SCREEN", 0);
     if (ps.kt == 0 && screen_min > 0 && nch >= screen_min && Lp.nrb > 1) {
       GradArgs sa = a;
       const int tpg_s = 2 * GRAD_WAVES;
@@ -302,21 +350,67 @@ struct ViewBackend {
     } else {
       HIP_TRY(launch_k(ps.kt, a, dim3(Lp.nrb, Lp.groups)));
     }
+    if (ex.sh) {  // a row shard: the same fold, into the exchange's device buffer at the chunks' exchange positions
+      HIP_TRY(launch_grad_reduce_shard(dtype, ps.kt, (const double*)ctx->g_slab.p, Lp.nrb, nch,
+                                       (const int32_t*)ctx->g_chunks.p + 2 * nch, xbuf + sum_off[pi], xbuf + chk_off[pi],
+                                       ctx->stream));
+      return SRHIP_OK;
+    }
     // the reduction writes the records straight into coherent pinned host memory (no copy on the stream)
     HIP_TRY(launch_grad_reduce(dtype, ps.kt, (const double*)ctx->g_slab.p, Lp.nrb, nch, (double*)ctx->h_gred[pi].p,
                                ctx->stream));
     return SRHIP_OK;
   }
 
-  double wsum(const GradItem&) const { return ds->weighted ? v.sum_w : (double)v.m; }
-  const double* decide_inputs(const GradItem&) { return sums.data(); }
+  bool host_records() const { return !ex.sh; }
+
+  int collect(GradPass (&pass)[2]) {
+    if (!ex.sh) {
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      return SRHIP_OK;
+    }
+    // the exchange: no host wait in front of it, one behind it; then each pass's records back in the
+    // (kt + 2)-per-chunk layout, by launch position
+    const void* red = nullptr;
+    const int rc = ex.sh->io->reduce(xl, ctx->stream, &red);
+    if (rc) return rc;
+    const double* const r = (const double*)red;
+    for (int pi = 0; pi < 2; ++pi) {
+      GradPass& ps = pass[pi];
+      const size_t nch = ps.chunks.size(), w = (size_t)ps.kt + 2;
+      if (nch == 0) continue;
+      xred[pi].resize(nch * w);
+      for (size_t c = 0; c < nch; ++c) {
+        const size_t at = (size_t)ps.chunks[c].pos;
+        std::copy(r + sum_off[pi] + at * (w - 1), r + sum_off[pi] + (at + 1) * (w - 1), xred[pi].begin() + c * w);
+        xred[pi][c * w + w - 1] = r[chk_off[pi] + at];
+      }
+      ps.red = xred[pi].data();
+    }
+    return SRHIP_OK;
+  }
+
+  double wsum(const GradItem&) const {
+    if (ex.raw_chk) return 1.0;  // (the raw sums: x / 1.0 is x)
+    if (ex.sh) return ex.sh->wsum;
+    return ds->weighted ? v.sum_w : (double)v.m;
+  }
+  int decide(const GradItem& it, double chk) {
+    if (ex.raw_chk) {
+      ex.raw_chk[it.tree] = chk;
+      return 0;
+    }
+    return decide_tree(P->ginfo[it.slot], *P, ds->nfeat, sums.data(), chk);
+  }
 
   // near-overflow sums: the exact per-operator-node pass on the gradient program decides, so the
   // objective is eval_loss's (L(Inf) exactly where did_succeed fails); one batched pass over the view
+  // (a row shard: over this rank's rows, the per-operator sums summed over the ranks before the verdict)
   int settle(const std::vector<GradItem>& items, const std::vector<int32_t>& und, uint8_t* ok) {
     std::vector<int32_t> slots;
     for (int32_t ui : und) slots.push_back(items[ui].slot);
-    return precise_decide(ctx, ds, P, v, slots.data(), (int32_t)slots.size(), true, ok);
+    return precise_decide(ctx, ds, P, v, slots.data(), (int32_t)slots.size(), true, ok,
+                          ex.sh ? &ex.sh->io->reduce_host : nullptr);
   }
 };
 
@@ -389,10 +483,17 @@ struct RowsetBackend {
     return SRHIP_OK;
   }
 
+  bool host_records() const { return true; }
+
+  int collect(GradPass (&)[2]) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SRHIP_OK;
+  }
+
   double wsum(const GradItem& it) const { return ds->weighted ? rb.wsum[it.tree] : (double)rb.m[it.tree]; }
-  const double* decide_inputs(const GradItem& it) {
+  int decide(const GradItem& it, double chk) {
     fill_decide_inputs(sums.data(), P->ntrees, ds->nfeat, rb.fstat.data() + (size_t)it.tree * ds->nfeat, rb.m[it.tree]);
-    return sums.data();
+    return decide_tree(P->ginfo[it.slot], *P, ds->nfeat, sums.data(), chk);
   }
 
   // (rare) the exact per-operator-node pass on a view made from each item's own set
@@ -444,7 +545,8 @@ static int eval_grad_items_on(srhip_ctx* ctx, srhip_program* P, Backend& be, con
     if (P->ginfo[it.slot].static_fail) continue;
     GradPass& ps = pass[it.value_only ? 1 : 0];
     const int span = it.value_only ? 1 : std::max(nc, 1);
-    for (int c0 = 0; c0 < span; c0 += std::max(ps.kt, 1)) ps.chunks.push_back(Chunk{it.slot, c0, (int32_t)i, it.tree});
+    for (int c0 = 0; c0 < span; c0 += std::max(ps.kt, 1))
+      ps.chunks.push_back(Chunk{it.slot, c0, (int32_t)i, it.tree, (int32_t)ps.chunks.size()});
   }
   if (pass[0].chunks.empty() && pass[1].chunks.empty()) {  // a patched gradient program may still be uploading from P->gcode
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -456,17 +558,21 @@ static int eval_grad_items_on(srhip_ctx* ctx, srhip_program* P, Backend& be, con
   for (int pi = 0; pi < 2; ++pi) {
     GradPass& ps = pass[pi];
     if (ps.chunks.empty()) continue;
-    HIP_TRY(ctx->h_gred[pi].ensure(ps.chunks.size() * (ps.kt + 2) * sizeof(double), hipHostMallocCoherent));
+    // the records' home: the context's coherent staging, which the reduction writes -- or, on a row shard,
+    // the exchange's reduced copy, which collect() points ps.red at
+    const bool staged = be.host_records();
+    if (staged) HIP_TRY(ctx->h_gred[pi].ensure(ps.chunks.size() * (ps.kt + 2) * sizeof(double), hipHostMallocCoherent));
     rc = be.launch(pi, ps, first && timed ? ctx->ev0 : nullptr);
     if (rc) return rc;
     first = false;
-    ps.red = (const double*)ctx->h_gred[pi].p;
+    if (staged) ps.red = (const double*)ctx->h_gred[pi].p;
   }
   if (timed) HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
   ctx->timed = timed;
   ctx->last_ev0 = ctx->ev0;
   ctx->last_ev1 = ctx->ev1;
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  rc = be.collect(pass);
+  if (rc) return rc;
   std::vector<int32_t> undecided;  // items
   for (const GradPass& ps : pass) {
     const int nch = (int)ps.chunks.size();
@@ -478,7 +584,7 @@ static int eval_grad_items_on(srhip_ctx* ctx, srhip_program* P, Backend& be, con
       const double wsum = be.wsum(it);
       for (int j = 0; j < ps.kt && ch.c0 + j < nc; ++j) it.g[ch.c0 + j] = r[1 + j] / wsum;
       if (ch.c0 == 0) {
-        const int st = decide_tree(P->ginfo[it.slot], *P, be.ds->nfeat, be.decide_inputs(it), r[ps.kt + 1]);
+        const int st = be.decide(it, r[ps.kt + 1]);
         *it.f = st == 1 ? INFINITY : r[0] / wsum;
         if (it.ok) *it.ok = st != 1;
         if (st == 2) undecided.push_back(ch.item);
@@ -506,12 +612,13 @@ static int eval_grad_items_on(srhip_ctx* ctx, srhip_program* P, Backend& be, con
 }
 // on the view's rows, or (rb given: it replaces the view) every item on its tree's own row set
 static int eval_grad_items(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss,
-                           const View& v, const std::vector<GradItem>& items, bool timed, const RowsetBatch* rb) {
+                           const View& v, const std::vector<GradItem>& items, bool timed, const RowsetBatch* rb,
+                           const GradExtra& ex) {
   if (rb) {
     RowsetBackend be{ctx, ds, P, loss, *rb};
     return eval_grad_items_on(ctx, P, be, items, timed);
   }
-  ViewBackend be{ctx, ds, P, loss, v};
+  ViewBackend be{ctx, ds, P, loss, v, ex};
   return eval_grad_items_on(ctx, P, be, items, timed);
 }
 
@@ -565,7 +672,7 @@ static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, 
                      const std::vector<int32_t>& trees, const std::vector<int64_t>& coff, double* f, double* g,
                      uint8_t* ok = nullptr, const std::vector<GradItem>* extra = nullptr, int64_t spec_lo = 0,
                      int64_t spec_hi = -1, const uint8_t* value_only = nullptr, bool timed = true,
-                     const RowsetBatch* rb = nullptr) {
+                     const RowsetBatch* rb = nullptr, const GradExtra& ex = GradExtra()) {
   const double t0 = now_s();
   int rc = compile_grad_program(*P);
   g_t_compile += now_s() - t0;
@@ -581,7 +688,7 @@ static int eval_grad(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, 
     // h_gpatch) can be in flight before the same launch; synchronised with the launch in eval_grad_items
     const int urc = upload_gcode(ctx, *P, spec_lo, spec_hi, ctx->h_gspec);
     if (urc) return urc;
-    return eval_grad_items(ctx, ds, P, loss, v, items, timed, rb);
+    return eval_grad_items(ctx, ds, P, loss, v, items, timed, rb, ex);
   };
   rc = body();
   // a patched gradient program's upload (compile_grad_program) may still be in flight from P->gcode:
@@ -625,6 +732,7 @@ struct DeviceEvaluator {
   const LossSel& loss;
   const View& v;
   const RowsetBatch* rb;
+  GradExtra ex;  // a row shard's exchange: every evaluation of the run is one exchange
   std::vector<GradItem> sitems = {};
   int64_t spec_lo = INT64_MAX, spec_hi = -1;  // the instructions the launch's slots rewrote
   double t0 = 0.0, t1 = 0.0, t2 = 0.0;
@@ -663,7 +771,7 @@ struct DeviceEvaluator {
                                 b.knobs.value_trials});
     t1 = now_s();
     const int rc = eval_grad(ctx, ds, P, loss, v, b.act, b.coff, b.fe.data(), b.ge.data(), nullptr, &sitems, spec_lo,
-                             spec_hi, b.vonly.data(), /*timed=*/false, rb);
+                             spec_hi, b.vonly.data(), /*timed=*/false, rb, ex);
     if (rc) return rc;
     if (loss.expr) {
       // an expression's loss is no failure where it is not finite (did_succeed is the tree's alone), so NaN and
@@ -704,14 +812,14 @@ static int bfgs_pipelined(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program
                           const View& v, const std::vector<int32_t>& trees, const std::vector<int64_t>& coff,
                           int iterations, double g_tol, const std::vector<std::vector<double>>& starts,
                           std::vector<double>& best_x, std::vector<double>& best_f, std::vector<int64_t>& fcalls,
-                          const RowsetBatch* rb = nullptr) {
+                          const RowsetBatch* rb = nullptr, const GradShardCall* sh = nullptr) {
   const BfgsKnobs knobs = bfgs_knobs(iterations, g_tol);
   BfgsBatch batch(P->ntrees, trees, coff, starts, knobs, best_x, best_f, fcalls);
   if (P->gspec_cap != knobs.spec_slots) {
     P->gspec_cap = knobs.spec_slots;  // the next gradient compile allocates the slots (a full compile)
     P->grad_ready = false;
   }
-  DeviceEvaluator ev{ctx, ds, P, loss, v, rb};
+  DeviceEvaluator ev{ctx, ds, P, loss, v, rb, GradExtra{sh, nullptr}};
   const int rc = bfgs_run(batch, ev);
   g_nonfinite_trials += batch.stats.nonfinite_trials;
   g_spec_launched += batch.stats.spec_launched;
@@ -1067,7 +1175,8 @@ int install_and_rescore(srhip_program& P, bool expr, const std::vector<double>& 
 template <class Score>
 int optimize_starts(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const LossSel& loss, Score score,
                     const int64_t* idx, int64_t nidx, const srhip_optim_options* opt, const double* starts_in,
-                    double* starts_out, double* out_loss, uint8_t* out_improved, int64_t* out_fcalls) {
+                    double* starts_out, double* out_loss, uint8_t* out_improved, int64_t* out_fcalls,
+                    const GradShardCall* sh = nullptr) {
   int rc;
   HIP_TRY(hipSetDevice(ctx->device));
   const int32_t nt = P->ntrees;
@@ -1110,7 +1219,10 @@ int optimize_starts(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, c
     const double tb = now_s();
     const char* te = getenv("SRHIP_OPTIM_TIMING");
     reset_optim_counters(te && (*te == '2' || *te == '3'), te && *te == '3');
-    rc = optimize_split(ctx, ds, P, loss, v, trees, coff, opt->iterations, g_tol, starts, best_x, best_f, fcalls);
+    // a row shard runs one group on the caller's context and thread: a communicator carries one exchange at a time
+    rc = sh ? bfgs_pipelined(ctx, ds, P, loss, v, trees, coff, opt->iterations, g_tol, starts, best_x, best_f, fcalls,
+                             nullptr, sh)
+            : optimize_split(ctx, ds, P, loss, v, trees, coff, opt->iterations, g_tol, starts, best_x, best_f, fcalls);
     if (g_stats_on)
       fprintf(stderr, "srhip optim (the caller's group: 1 of SRHIP_OPTIM_SPLIT groups): launches by active trees: "
               "1: %lld, 2-4: %lld, 5-16: %lld, 17-64: %lld, >64: %lld; "
@@ -1204,6 +1316,174 @@ int srhip_optimize_constants(srhip_ctx* ctx, const srhip_dataset* ds, srhip_prog
                              uint8_t* out_improved, int64_t* out_fcalls) {
   return srhip_optimize_constants_starts(ctx, ds, P, loss, idx, nidx, opt, nullptr, nullptr, out_loss, out_improved,
                                          out_fcalls);
+}
+
+}  // extern "C"
+
+// ---- row shards: srhip_eval_loss_grad_sharded / srhip_optimize_constants_sharded / the manual steps ---------
+namespace {
+
+// this rank's view of its own rows, as the one-device entry points make it
+int shard_view(srhip_ctx* ctx, const srhip_dataset* ds, const int64_t* idx, int64_t nidx, View& v) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int rc = make_view(ctx, ds, idx, nidx, true, v);
+  if (rc) return rc;
+  return idx && ds->weighted ? gathered_weight_sum(ctx, ds, nidx, v) : SRHIP_OK;
+}
+
+// The call-start exchange, one group: [weight sum or rows | per feature {column sum, non-finite count} | rows] by
+// SUM and the call's signature [k_i, -k_i] by MAX.  Every rank returns SRHIP_ERR_INVALID naming the first field the
+// ranks disagree on, before any per-round exchange: ranks that would build different launches fail at once
+// instead of waiting out the communicator's timeout inside a collective.
+int shard_call_start(const srhip_dataset* ds, const View& v, const GradShardIO& io, const double (&sig)[SIG_COUNT],
+                     GradShardCall& sh) {
+  const size_t nf = (size_t)ds->nfeat;
+  std::vector<double> sum(2 + 2 * nf), mx(2 * (size_t)SIG_COUNT);
+  sum[0] = ds->weighted ? v.sum_w : (double)v.m;
+  for (size_t f = 0; f < nf; ++f) {
+    sum[1 + 2 * f] = v.stats ? v.stats[f].sum : 0.0;
+    sum[2 + 2 * f] = v.stats ? (double)v.stats[f].nonfinite : 0.0;
+  }
+  sum[1 + 2 * nf] = (double)v.m;
+  for (int i = 0; i < SIG_COUNT; ++i) {
+    mx[2 * i] = sig[i];
+    mx[2 * i + 1] = -sig[i];
+  }
+  const int rc = io.start(sum.data(), sum.size(), mx.data(), mx.size());
+  if (rc) return rc;
+  const int bad = shard_sig_check(mx.data(), SIG_COUNT);
+  if (bad >= 0)
+    return fail(SRHIP_ERR_INVALID, "the ranks of a row-sharded call disagree on its %s (every rank calls with the same "
+                                   "program, options, seed and SRHIP_* environment)", shard_sig_name(bad));
+  sh.io = &io;
+  sh.wsum = sum[0];
+  sh.tail.assign(sum.begin() + 1, sum.end());
+  return SRHIP_OK;
+}
+
+uint64_t fnv1a(const void* p, size_t n) {
+  uint64_t h = 1469598103934665603ull;
+  for (size_t i = 0; i < n; ++i) h = (h ^ ((const uint8_t*)p)[i]) * 1099511628211ull;
+  return h;
+}
+uint64_t f64_bits(double x) {
+  uint64_t b;
+  memcpy(&b, &x, 8);
+  return b;
+}
+
+// the fields every sharded entry point shares
+void shard_signature(const srhip_dataset* ds, const srhip_program* P, const srhip_loss* loss, int entry,
+                     double (&sig)[SIG_COUNT]) {
+  for (double& s : sig) s = 0.0;
+  sig[SIG_ENTRY] = entry;
+  sig[SIG_TREES] = P->ntrees;
+  sig[SIG_CONSTS] = (double)const_offsets(*P).back();
+  sig[SIG_DTYPE] = P->dtype;
+  sig[SIG_WEIGHTED] = ds->weighted ? 1 : 0;
+  sig[SIG_LOSS_KIND] = loss->kind;
+  shard_sig_put64(sig, SIG_LOSS_P0_HI, f64_bits(loss->p0));
+  shard_sig_put64(sig, SIG_LOSS_P1_HI, f64_bits(loss->p1));
+  const char* kte = env_get("SRHIP_GRAD_KT");
+  sig[SIG_GRAD_KT] = kte && (atoi(kte) == 4 || atoi(kte) == GRAD_KT) ? atoi(kte) : 0;
+}
+
+}  // namespace
+
+int srhip::run_grad_sharded(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                            const int64_t* idx, int64_t nidx, const GradShardIO& gio, double* out_loss, double* out_grad,
+                            uint8_t* out_ok) {
+  if (!out_loss || !out_grad || !out_ok) return fail(SRHIP_ERR_INVALID, "null output");
+  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant gradients need Float32 / Float64");
+  View v;
+  rc = shard_view(ctx, ds, idx, nidx, v);
+  if (rc) return rc;
+  double sig[SIG_COUNT];
+  shard_signature(ds, P, loss, 0, sig);
+  GradShardCall sh;
+  rc = shard_call_start(ds, v, gio, sig, sh);
+  if (rc) return rc;
+  rc = derived_view(ctx, ds, P, v);
+  if (rc) return rc;
+  const std::vector<int64_t> coff = const_offsets(*P);
+  std::vector<int32_t> all(P->ntrees);
+  std::iota(all.begin(), all.end(), 0);
+  return eval_grad(ctx, ds, P, loss, v, all, coff, out_loss, out_grad, out_ok, nullptr, 0, -1, nullptr, true, nullptr,
+                   GradExtra{&sh, nullptr});
+}
+
+int srhip::run_optimize_sharded(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                                const int64_t* idx, int64_t nidx, const srhip_optim_options* opt, const double* starts_in,
+                                double* starts_out, const ShardIO& eio, const GradShardIO& gio, double* out_loss,
+                                uint8_t* out_improved, int64_t* out_fcalls) {
+  if (!opt || !out_loss || !out_improved) return fail(SRHIP_ERR_INVALID, "null argument");
+  int rc = check_optim_args(ctx, ds, P, loss, opt);
+  if (rc) return rc;
+  GradShardCall sh;
+  {
+    // the call-start exchange on a view of its own, in front of the baseline: the signature is checked before
+    // anything whose size depends on it is exchanged (optimize_starts makes the view again after its baseline,
+    // whose evaluation gathers into the same buffers)
+    View v;
+    rc = shard_view(ctx, ds, idx, nidx, v);
+    if (rc) return rc;
+    double sig[SIG_COUNT];
+    shard_signature(ds, P, loss, 1, sig);
+    const BfgsKnobs k = bfgs_knobs(opt->iterations, opt->g_tol > 0 ? opt->g_tol : 1e-8);
+    sig[SIG_ITERATIONS] = opt->iterations;
+    sig[SIG_RESTARTS] = opt->nrestarts;
+    shard_sig_put64(sig, SIG_SEED_HI, opt->seed);
+    shard_sig_put64(sig, SIG_GTOL_HI, f64_bits(k.g_tol));
+    const size_t nstart = (size_t)opt->nrestarts * (size_t)const_offsets(*P).back();
+    shard_sig_put64(sig, SIG_STARTS_HI, starts_in && nstart ? fnv1a(starts_in, nstart * sizeof(double)) : 0);
+    sig[SIG_VALUE_TRIALS] = k.value_trials ? 1 : 0;
+    sig[SIG_SPEC_SLOTS] = k.spec_slots;
+    sig[SIG_SPEC_ACTIVE] = k.spec_max_active;
+    sig[SIG_SPEC_DEPTH] = k.spec_max_depth;
+    rc = shard_call_start(ds, v, gio, sig, sh);
+    if (rc) return rc;
+  }
+  auto score = [&](double* l, uint8_t* ok) { return run_eval_sharded(ctx, ds, P, loss, idx, nidx, eio, l, ok); };
+  return optimize_starts(ctx, ds, P, LossSel(loss), score, idx, nidx, opt, starts_in, starts_out, out_loss, out_improved,
+                         out_fcalls, &sh);
+}
+
+extern "C" {
+
+int srhip_eval_loss_grad_partials(srhip_ctx* ctx, const srhip_dataset* ds, srhip_program* P, const srhip_loss* loss,
+                                  const int64_t* idx, int64_t nidx, double* sums, double* gsums, double* chk) {
+  if (!sums || !chk) return fail(SRHIP_ERR_INVALID, "null output");
+  int rc = check_eval_args(ctx, ds, P, MODE_LOSS, loss);
+  if (rc) return rc;
+  if (P->dtype == SRHIP_I32) return fail(SRHIP_ERR_UNSUPPORTED, "constant gradients need Float32 / Float64");
+  const std::vector<int64_t> coff = const_offsets(*P);
+  if (!gsums && coff.back() > 0) return fail(SRHIP_ERR_INVALID, "null gradient sums");
+  View v;
+  rc = shard_view(ctx, ds, idx, nidx, v);
+  if (rc) return rc;
+  rc = derived_view(ctx, ds, P, v);
+  if (rc) return rc;
+  const int32_t nt = P->ntrees;
+  std::vector<int32_t> all(nt);
+  std::iota(all.begin(), all.end(), 0);
+  std::vector<double> f(nt), g(std::max<int64_t>(1, coff.back()));
+  for (int32_t t = 0; t < nt; ++t) chk[t] = 0.0;
+  // the raw records: sums undivided (the backend divides by 1), no decision, each tree's statistic into chk
+  rc = eval_grad(ctx, ds, P, loss, v, all, coff, f.data(), g.data(), nullptr, nullptr, 0, -1, nullptr, true, nullptr,
+                 GradExtra{nullptr, chk});
+  if (rc) return rc;
+  const double wsum = ds->weighted ? v.sum_w : (double)v.m;
+  for (int32_t t = 0; t < nt; ++t) {
+    sums[2 * (size_t)t] = P->ginfo[t].static_fail ? 0.0 : f[t];  // (a static failure launches nothing: no sum)
+    sums[2 * (size_t)t + 1] = wsum;
+    // a non-finite Float32 statistic travels as +Inf: a MAX across shards need not keep a NaN
+    if (P->dtype == SRHIP_F32 && !std::isfinite(chk[t])) chk[t] = INFINITY;
+  }
+  fill_decide_inputs(sums, nt, ds->nfeat, v.stats, v.m);
+  std::copy(g.begin(), g.begin() + coff.back(), gsums);
+  return SRHIP_OK;
 }
 
 }  // extern "C"

@@ -187,6 +187,14 @@ SIGNATURES = {
     "srhip_comm_migrate_start": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32]),
     "srhip_comm_migrate_wait": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "srhip_eval_loss_sharded": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, _vp, _vp]),
+    "srhip_eval_loss_grad_sharded": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, _vp, _vp, _vp]),
+    "srhip_optimize_constants_sharded": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64,
+                                                        ctypes.POINTER(OptimOptions), _vp, _vp, _vp, _vp, _vp]),
+    "srhip_eval_loss_grad_partials": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(Loss), _vp, _i64, _vp, _vp, _vp]),
+    "srhip_grad_partials_finalize": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srhip_shard_signature_check": (_i32, [_vp, _i32]),
+    "srhip_shard_signature_fields": (_i32, []),
+    "srhip_shard_signature_field_name": (ctypes.c_char_p, [_i32]),
     "srhip_last_kernel_ms": (_dbl, [_vp]),
     "srhip_last_work": (ctypes.c_int, [_vp, ctypes.POINTER(_i64)]),
     "srhip_hot_form_launches": (ctypes.c_int64, [_vp]),

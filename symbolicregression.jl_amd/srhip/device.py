@@ -477,6 +477,38 @@ class Program:
         check(_lib.load().srhip_precise_finalize(self.handle, ptr(trees), len(trees), ptr(opsums), ptr(ok)))
         return ok.astype(bool)
 
+    # ---- row-sharded constant gradients (include/srhip.h "the manual steps") --------------------
+    def eval_loss_grad_partials(self, ds: DeviceDataset, loss, idx=None):
+        """This shard's (sums[2T + 2F + 1], gsums[sum nconst], chk[T]) of the gradient kernels -- combine
+        across shards (sums and gsums by SUM, chk by chk_reduce_op()), then finalize_grad()."""
+        sums = np.empty(2 * self.ntrees + 2 * ds.nfeatures + 1, dtype=np.float64)
+        gsums = np.empty(int(self.num_constants().sum()), dtype=np.float64)
+        chk = np.empty(self.ntrees, dtype=np.float64)
+        ls = loss.c_struct()
+        idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        check(_lib.load().srhip_eval_loss_grad_partials(self.ctx.handle, ds.handle, self.handle, ctypes.byref(ls),
+                                                        ptr(idxa), 0 if idxa is None else len(idxa), ptr(sums),
+                                                        ptr(gsums), ptr(chk)))
+        return sums, gsums, chk
+
+    def finalize_grad(self, nfeatures: int, sums, gsums, chk):
+        """Loss and gradient from globally combined partials (srhip_grad_partials_finalize, no device):
+        (loss[T], grads: list of per-tree arrays, ok[T], status[T]); a failing tree is +Inf with a zero slice;
+        status 2 = undecided (settle it with eval_precise_partials / precise_finalize)."""
+        nconst = self.num_constants()
+        sums = np.ascontiguousarray(sums, dtype=np.float64)
+        gsums = np.ascontiguousarray(gsums, dtype=np.float64)
+        chk = np.ascontiguousarray(chk, dtype=np.float64)
+        if sums.size != 2 * self.ntrees + 2 * int(nfeatures) + 1 or gsums.size != int(nconst.sum()) or chk.size != self.ntrees:
+            raise ValueError("partials do not have the program's sizes")
+        loss = np.empty(self.ntrees, dtype=np.float64)
+        grad = np.empty(int(nconst.sum()), dtype=np.float64)
+        ok = np.empty(self.ntrees, dtype=np.uint8)
+        st = np.empty(self.ntrees, dtype=np.uint8)
+        check(_lib.load().srhip_grad_partials_finalize(self.handle, int(nfeatures), ptr(sums), ptr(gsums), ptr(chk),
+                                                       ptr(loss), ptr(grad), ptr(ok), ptr(st)))
+        return loss, np.split(grad, np.cumsum(nconst)[:-1]), ok.astype(bool), st
+
     def close(self):
         if self.handle:
             _lib.load().srhip_program_destroy(self.handle)

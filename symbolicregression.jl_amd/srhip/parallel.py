@@ -161,6 +161,34 @@ def eval_loss_sharded(prog, nfeatures: int, partials, precise=None, group=None):
     return loss, ok
 
 
+def eval_loss_grad_sharded(prog, nfeatures: int, partials, precise=None, group=None):
+    """Row-sharded eval_loss_grad for every tree of ``prog`` over torch.distributed.
+
+    partials(): this rank's (sums, gsums, chk) — ``prog.eval_loss_grad_partials(shard, loss)`` on a GPU;
+    precise(trees): this rank's per-operator sums for undecided trees —
+    ``prog.eval_precise_partials(shard, trees)``.  One device buffer [sums | gsums | chk] and one exchange
+    (SUM over the sums, MAX for Float32 / SUM over the check statistics), one more only when a tree is
+    undecided.  Returns (loss[T], grads: list of per-tree arrays, ok[T]) identical on all ranks; a failing
+    tree is +Inf with a zero slice."""
+    sums, gsums, chk = partials()
+    ns = len(sums)
+    both, chk = allreduce_partials(np.concatenate([np.asarray(sums, np.float64), np.asarray(gsums, np.float64)]), chk,
+                                   "max" if prog.chk_reduce_op() == "max" else "sum", group)
+    sums, gsums = both[:ns], both[ns:]
+    loss, grads, ok, status = prog.finalize_grad(nfeatures, sums, gsums, chk)
+    undecided = np.nonzero(status == 2)[0].astype(np.int32)
+    if len(undecided):
+        if precise is None:
+            raise RuntimeError("undecided overflow checks need the precise pass (pass precise=...)")
+        opsums = allreduce_np(precise(undecided), "sum", group)
+        uok = prog.precise_finalize(undecided, opsums)
+        for t, good in zip(undecided, uok):
+            if not good:
+                ok[t], loss[t] = False, np.inf
+                grads[t][:] = 0.0
+    return loss, grads, ok
+
+
 def allgather_trees(nodes: np.ndarray, offsets: np.ndarray, group=None):
     """Migration exchange: every rank's trees (srhip_node tables) -> list of (nodes, offsets) by rank."""
     import torch
@@ -646,6 +674,57 @@ class NativeComm:
         timer.seconds += time.perf_counter() - t0
         timer.calls += 1
         return out, ok.astype(bool)
+
+    def eval_loss_grad_sharded(self, prog, ds, loss, idx=None):
+        """Row-sharded eval_loss_grad over this rank's rows (srhip_eval_loss_grad_sharded): (loss[T], grads:
+        list of per-tree arrays in get_constants order, ok[T]) over all ranks' rows, identical on every rank."""
+        import ctypes
+        import time
+
+        from . import _lib
+
+        t0 = time.perf_counter()
+        nconst = prog.num_constants()
+        out = np.empty(prog.ntrees, dtype=np.float64)
+        grad = np.empty(int(nconst.sum()), dtype=np.float64)
+        ok = np.empty(prog.ntrees, dtype=np.uint8)
+        ls = loss.c_struct()
+        idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        _lib.check(_lib.load().srhip_eval_loss_grad_sharded(self.ctx.handle, self.handle, ds.handle, prog.handle,
+                                                             ctypes.byref(ls), _lib.ptr(idxa),
+                                                             0 if idxa is None else len(idxa), _lib.ptr(out),
+                                                             _lib.ptr(grad), _lib.ptr(ok)))
+        timer.seconds += time.perf_counter() - t0
+        timer.calls += 1
+        return out, np.split(grad, np.cumsum(nconst)[:-1]), ok.astype(bool)
+
+    def optimize_constants_sharded(self, prog, ds, loss, iterations=8, nrestarts=2, seed=0, g_tol=1e-8, idx=None,
+                                   starts=None, return_starts=False):
+        """Row-sharded optimize_constants (srhip_optimize_constants_sharded): the objective is the loss over all
+        ranks' rows; updates prog's constants in place, the same on every rank.  Arguments and return shapes as
+        Program.optimize_constants; every rank passes the same options, seed and starts."""
+        import ctypes
+
+        from . import _lib
+
+        opt = _lib.OptimOptions(int(iterations), int(nrestarts), int(seed) & (2**64 - 1), float(g_tol))
+        out = np.empty(prog.ntrees, dtype=np.float64)
+        imp = np.empty(prog.ntrees, dtype=np.uint8)
+        fc = np.empty(prog.ntrees, dtype=np.int64)
+        ls = loss.c_struct()
+        idxa = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        nall = int(prog.num_constants().sum())
+        sin = None
+        if starts is not None:
+            sin = np.ascontiguousarray(starts, dtype=np.float64).reshape(int(nrestarts), nall)
+        sout = np.empty((int(nrestarts), nall), dtype=np.float64) if return_starts else None
+        _lib.check(_lib.load().srhip_optimize_constants_sharded(
+            self.ctx.handle, self.handle, ds.handle, prog.handle, ctypes.byref(ls), _lib.ptr(idxa),
+            0 if idxa is None else len(idxa), ctypes.byref(opt), _lib.ptr(sin), _lib.ptr(sout), _lib.ptr(out),
+            _lib.ptr(imp), _lib.ptr(fc)))
+        if return_starts:
+            return out, imp.astype(bool), fc, sout
+        return out, imp.astype(bool), fc
 
     def stats(self):
         """(ms of the last exchange, ms in all exchanges, exchanges) -- host wall time, issue to completion

@@ -10,7 +10,8 @@
 // populations at once (srhip_compile.cpp) -- the persistent host pool, the 64-shard code cache with its first-sighting
 // table (populations recur, so trees are cached on their second sighting and hit from their third),
 // background teardown -- query and set constants, run srhip_partials_finalize, srhip_precise_finalize and
-// srhip_decide_rowset over random partials,
+// srhip_decide_rowset over random partials, the row-sharded gradient's srhip_grad_partials_finalize and
+// srhip_shard_signature_check,
 // and feed malformed node tables (bad children, bad operator indices) that must fail cleanly.
 // Device phase (only when a device is visible): concurrent clients of the cross-population coalescer
 // (srhip_batcher: per-request completion, two worker contexts), submitted evaluations waited out of
@@ -161,6 +162,39 @@ static void host_worker(int id, int rounds, const std::vector<Population>* pops)
       double applied = 0.0;
       const double raw = chk[t] > 3.0e38 ? INFINITY : chk[t];  // (a Float32 statistic)
       CHECK(srhip_decide_rowset(P, t, nf, 1 + (int64_t)(rng() % 5000), fst.data(), raw, &status[t], &applied));
+    }
+    // the row-sharded gradient's device-free steps: the finalize over the same random partials (a host-only
+    // program compiles its gradient program here) and the call signature's comparison
+    {
+      std::vector<double> gsums((size_t)total), gl(nt), gg((size_t)total + 1);
+      for (double& g : gsums) g = std::ldexp((double)(rng() % 2001) - 1000.0, -4);
+      CHECK(srhip_grad_partials_finalize(P, nf, sums.data(), gsums.data(), chk.data(), gl.data(), gg.data(), ok.data(),
+                                         status.data()));
+      int64_t g0 = 0;
+      for (int32_t t = 0; t < nt; ++t) {
+        for (int32_t k = 0; k < nconst[t]; ++k)
+          if (status[t] == 1 ? gg[g0 + k] != 0.0 : gg[g0 + k] != gsums[g0 + k] / 4096.0) {
+            fprintf(stderr, "FAIL gradient finalize: tree %d constant %d status %d\n", t, k, (int)status[t]);
+            g_fail = 1;
+          }
+        g0 += nconst[t];
+      }
+      const int32_t nsig = srhip_shard_signature_fields();
+      std::vector<double> sig(2 * (size_t)nsig);
+      for (int32_t i = 0; i < nsig; ++i) {
+        sig[2 * i] = (double)(rng() % 1000);
+        sig[2 * i + 1] = -sig[2 * i];
+      }
+      const int32_t odd = (int32_t)(rng() % (uint64_t)nsig);
+      if (srhip_shard_signature_check(sig.data(), nsig) != -1 || !srhip_shard_signature_field_name(odd)) {
+        fprintf(stderr, "FAIL signature check: agreeing ranks reported\n");
+        g_fail = 1;
+      }
+      sig[2 * odd + 1] += 1.0;  // another rank held a smaller value of this field
+      if (srhip_shard_signature_check(sig.data(), nsig) != odd) {
+        fprintf(stderr, "FAIL signature check: field %d not named\n", odd);
+        g_fail = 1;
+      }
     }
     srhip_program_destroy(P);  // (background teardown)
     // the launch decision over random shapes (srhip_plan_eval: arithmetic on sizes, no device)
