@@ -487,6 +487,26 @@ SRM_FN int srm_jrem_pio2f(float x, double* y) {
 SRM_FN double srm_jfn(double xd) { return srm_rint(xd * SRM_JINV_PIO2); }
 SRM_FN double srm_jred_near(double xd, double fn) { return xd - fn * SRM_JPIO2; }
 SRM_FN double srm_jred_cw(double xd, double fn) { return (xd - fn * SRM_JPIO2_1) - fn * SRM_JPIO2_1T; }
+/* The same reduction with its first step fused: fn * SRM_JPIO2_1 is exact (a 25-bit constant times
+ * |fn| < 2^28), so the fma rounds the same difference once -- srm_jred_cw's double on every float below
+ * 2^28 pi/2 (tools/check_trig_quadrant.c); three device instructions for four. */
+SRM_FN double srm_jred_cw_fma(double xd, double fn) { return srm_fma(-fn, SRM_JPIO2_1, xd) - fn * SRM_JPIO2_1T; }
+/* The quadrant word: with n1 = n + 1 - kind (bit 0: the cos kernel applies; bit 1: the sign),
+ * fn/2 + (1 - kind)/2 = n1/2 added to 1.5 * 2^21 is exact and stays in [2^21, 2^22) while
+ * -2^21 <= n1 < 2^21, where one Float64 ulp is 2^-31: the low 32 bits of that double are n1 << 30, so
+ * bit 30 is n1 & 1 and bit 31 is (n1 >> 1) & 1 -- one fma where the integer form converts, adds and
+ * shifts.  The device uses it for |fn| < 2^20: every |x| < SRM_JQW_MAXF, the smallest float whose
+ * fn reaches 2^20 (so no larger bound keeps |fn| < 2^20; the checker proves both).  The wide word
+ * (1.5 * 2^30: one ulp 2^-22) carries the same two bits at bits 21 and 22 for every |fn| < 2^28. */
+#define SRM_JQW_M 0x1.8p21
+#define SRM_JQW_WIDE_M 0x1.8p30
+#define SRM_JQW_MAXF 1647098.625f
+SRM_FN uint32_t srm_jqword(int kind, double fn) {
+  return (uint32_t)srm_bits(srm_fma(fn, 0.5, SRM_JQW_M + 0.5 * (1 - kind)));
+}
+SRM_FN uint32_t srm_jqword_wide(int kind, double fn) {
+  return (uint32_t)srm_bits(srm_fma(fn, 0.5, SRM_JQW_WIDE_M + 0.5 * (1 - kind)));
+}
 /* kind 0: cos, 1: sin of the reduced argument y in quadrant n: both kernels, one select and the sign */
 SRM_FN float srm_jtrigf_q(int kind, int n, double y) {
   const float fs = (float)srm_jsin_kernel(y), fc = (float)srm_jcos_kernel(y);

@@ -55,8 +55,17 @@
 #endif
 #define SRHIP_TRIG_ILP SRHIP_HEAVY_ILP  // rows Julia's Float32 trig bodies interleave (jtrigf_*); 1/2/4 measured alike (C2 1.278-1.289 ms)
 #endif
+#ifndef SRHIP_TRIG_CWFMA
+#define SRHIP_TRIG_CWFMA 1  // tier C's Cody-Waite reduction with its exact first step as one fma (srm_jred_cw_fma)
+#endif
+#ifndef SRHIP_TRIG_QWORD
+#define SRHIP_TRIG_QWORD 1  // the quadrant's parity and sign bits from one fma (srm_jqword); tier C ends at SRM_JQW_MAXF
+#endif
+#ifndef SRHIP_TRIG_ZEROWAVE
+#define SRHIP_TRIG_ZEROWAVE 1  // sin tiers B / C: the x == 0 rows (sin(-0) = -0) tested once per wave, not selected per row
+#endif
 #ifndef SRHIP_TRIG_ROWS
-#define SRHIP_TRIG_ROWS 1  // Float32 cos/sin/tan batched over the rows (trigf_rows)
+#define SRHIP_TRIG_ROWS 1 // Float32 cos/sin/tan batched over the rows (trigf_rows)
 #endif
 // Hot handlers (SRHIP_HOT_CASES): the switch's binary search is built weighted by case likelihood,
 // so the commonest handlers -- loads, pushes, + - * / in every operand form, the common unary
@@ -384,12 +393,14 @@ template <int R> __device__ __attribute__((always_inline)) inline bool trigf_row
 //   A  every |x| < Float32(pi)/4: no reduction, ONE kernel (sin: the sign of x copied onto it);
 //   B  every |x| <= pi*9/4: fn = rint(xd 2/pi), y = xd - fn (pi/2) (Julia's +-k pi/2 cases, one
 //      rounding), both kernels, the quadrant picks one and its sign;
-//   C  every |x| < 2^28 pi/2: per row Julia's choice between that y and its Cody-Waite reduction (cos:
-//      Cody-Waite for every row -- on every float it returns what the +-k pi/2 cases return; sin
-//      differs at x = +-3.0061);
-//   slow  any larger / Inf / NaN row: C for the rest, the scalar srm_jtrigf (Payne-Hanek) for those.
-// C2's cos-of-operator tiles fall 11 % / 47 % / 36 % / 6 % into A / B / C / slow
-// (scripts/trig_arg_tiers.py).
+//   C  every |x| < SRM_JQW_MAXF (|fn| < 2^20, the quadrant word's range; 2^28 pi/2 without the word): per
+//      row Julia's choice between that y and its Cody-Waite reduction (cos: Cody-Waite for every row --
+//      on every float it returns what the +-k pi/2 cases return; sin differs at x = +-3.0061);
+//   slow  any larger / Inf / NaN row: C's row with the wide word below 2^28 pi/2, the scalar srm_jtrigf
+//      (Payne-Hanek) for the rest.
+// C2's cos-of-operator tiles fall 11 % / 47 % / 36 % / 6 % into A / B / C / slow over all trees
+// (scripts/trig_arg_tiers.py); over the trees that run to the end 11.1 / 49.6 / 38.8 / 0.5 %
+// (scripts/trig_live_tiers.py).
 template <int KIND>
 __device__ __attribute__((always_inline)) inline float jtrigf_q_dev(double fn, double y) {
   const int n = cvt_i32_sat(fn);
@@ -413,6 +424,11 @@ __device__ __attribute__((always_inline)) inline RV<float, R> jtrigf_a_exact(RV<
   }
   return v;
 }
+// Julia's Cody-Waite reduction; its first step as one fma gives the same double on every float below
+// 2^28 pi/2 (fn * SRM_JPIO2_1 is exact; tools/check_trig_quadrant.c), three instructions for four
+__device__ __attribute__((always_inline)) inline double jred_cw_dev(double xd, double fn) {
+  return SRHIP_TRIG_CWFMA ? srm_jred_cw_fma(xd, fn) : srm_jred_cw(xd, fn);
+}
 template <int KIND, bool CW>
 __device__ __attribute__((always_inline)) inline double jtrigf_red(float x, double& fn) {
   const double xd = (double)x;
@@ -421,10 +437,10 @@ __device__ __attribute__((always_inline)) inline double jtrigf_red(float x, doub
   if constexpr (CW && KIND == 0) {
     // cos: the Cody-Waite reduction gives Julia's result on every float, the +-k pi/2 cases included
     // (tools/check_trigf.c), so a tier-C wave needs no per-row choice
-    y = srm_jred_cw(xd, fn);
+    y = jred_cw_dev(xd, fn);
   } else {
     y = srm_jred_near(xd, fn);
-    if constexpr (CW) y = __builtin_fabsf(x) <= SRM_J9PIO4F ? y : srm_jred_cw(xd, fn);
+    if constexpr (CW) y = __builtin_fabsf(x) <= SRM_J9PIO4F ? y : jred_cw_dev(xd, fn);
   }
   return y;
 }
@@ -508,42 +524,92 @@ __device__ __attribute__((noinline)) RV<float, R> jtrigf_a(RV<float, R> v) {
   }
   return v;
 }
-template <int KIND, bool CW>
-__device__ __attribute__((always_inline)) inline float jtrigf_row_fast(float x, double s4v, double c3v) {
+// The quadrant of a row: n1 = n + 1 - KIND, whose bit 0 selects the cos kernel (cos: n even; sin: n odd) and
+// whose bit 1 is the sign (cos: quadrants 1, 2; sin: 2, 3).  QW says where the two bits come from:
+//   QW_INT     cvt_i32(fn) + 1 - KIND, its bit 0 sign-extended, its bit 1 shift-added into bit 31: five
+//              instructions for cos, four for sin;
+//   QW_WORD    the low word of fma(fn, 0.5, 1.5 * 2^21 + (1 - KIND)/2) = n1 << 30 (srm_jqword: exact while
+//              |fn| < 2^20, every |x| < SRM_JQW_MAXF): the fma, a v_bfe_i32 of bit 30 and the sign as one
+//              v_bitop3_b32, bits ^ (word & 0x80000000) -- three instructions, tiers B and C;
+//   QW_WIDE    the same at 1.5 * 2^30 (srm_jqword_wide: bits 21 and 22, every |fn| < 2^28), one shift more:
+//              four instructions, the slow body's fast rows (cos saves one, sin as many as QW_INT).
+// tools/check_trig_quadrant.c proves each word's two bits and the composed row on every float it may see.
+enum { QW_INT = 0, QW_WORD = 1, QW_WIDE = 2 };
+constexpr int QW_BC = SRHIP_TRIG_QWORD ? QW_WORD : QW_INT, QW_SLOW = SRHIP_TRIG_QWORD ? QW_WIDE : QW_INT;
+// (0.5 is an inline constant and the addend the instruction's one scalar operand, as in fma_vvs)
+template <int KIND, int QW>
+__device__ __attribute__((always_inline)) inline uint32_t jqword_dev(double fn) {
+  double d;
+  asm("v_fma_f64 %0, %1, 0.5, %2" : "=v"(d) : "v"(fn), "s"((QW == QW_WIDE ? SRM_JQW_WIDE_M : SRM_JQW_M) + 0.5 * (1 - KIND)));
+  return (uint32_t)__builtin_bit_cast(uint64_t, d);
+}
+// the sign mask of the quadrant word in an SGPR, once per body (a VOP3 instruction takes no literal here)
+__device__ __attribute__((always_inline)) inline uint32_t jtrig_sign_sgpr() {
+  uint32_t sm = 0x80000000u;
+  asm volatile("" : "+s"(sm));
+  return sm;
+}
+// ZFIX: keep x where x == 0 -- sin(-0) = -0 is the one row the reduction gets wrong (y = +0)
+template <int KIND, bool CW, int QW, bool ZFIX = true>
+__device__ __attribute__((always_inline)) inline float jtrigf_row_fast(float x, double s4v, double c3v, uint32_t sm) {
   double fn;
   const double y = jtrigf_red<KIND, CW>(x, fn);
-  // n1 = n + 1 - KIND: its bit 0 selects the cos kernel (cos: n even; sin: n odd), its bit 1 is the sign
-  // (cos: quadrants 1, 2; sin: 2, 3)
-  const int n1 = cvt_i32_sat(fn) + 1 - KIND;
+  int n1 = 0;
+  uint32_t w = 0;
+  if constexpr (QW == QW_INT) n1 = cvt_i32_sat(fn) + 1 - KIND;
+  else w = jqword_dev<KIND, QW>(fn);
   const double z = y * y;
   const double ps = jsin_fma_dev(y, z, s4v), pc = jcos_fma_dev(z, c3v);
-  const int msk = __builtin_amdgcn_sbfe(n1, 0, 1);  // -1 where the cos kernel applies: a bit select, no compare
+  // -1 where the cos kernel applies: a bit select, no compare
+  const int msk = QW == QW_INT ? __builtin_amdgcn_sbfe(n1, 0, 1) : __builtin_amdgcn_sbfe((int)w, QW == QW_WORD ? 30 : 21, 1);
   double p = bfi_f64(msk, pc, ps);
   if (__builtin_amdgcn_ballot_w64(jtie_dev(p)) != 0) [[unlikely]]
     p = bfi_f64(msk, srm_jcos_kernel(y), srm_jsin_kernel(y));
-  // the sign added into bit 31 (the xor)
+  // the sign xored into bit 31
+  const uint32_t pb = __builtin_bit_cast(uint32_t, (float)p);
   uint32_t o;
-  asm("v_lshl_add_u32 %0, %1, 31, %2" : "=v"(o) : "v"(n1 >> 1), "v"(__builtin_bit_cast(uint32_t, (float)p)));
+  if constexpr (QW == QW_INT) {
+    asm("v_lshl_add_u32 %0, %1, 31, %2" : "=v"(o) : "v"(n1 >> 1), "v"(pb));
+  } else {
+    // a ^ (b & c).  (Inline, as the shift-add above: through the builtin the compiler sank every row's
+    // conversion and sign to the end of the body, sixteen rows' values live at once)
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x78" : "=v"(o) : "v"(pb), "v"(QW == QW_WORD ? w : w << 9), "s"(sm));
+  }
   const float r = __builtin_bit_cast(float, o);
-  return (KIND == 1 && x == 0.0f) ? x : r;  // sin(-0) = -0 (the reduction gives +0)
+  return (KIND == 1 && ZFIX && x == 0.0f) ? x : r;
 }
-template <int R, int KIND, bool CW>
-__device__ __attribute__((noinline)) RV<float, R> jtrigf_bc(RV<float, R> v) {
+template <int R, int KIND, bool CW, bool ZFIX>
+__device__ __attribute__((always_inline)) inline RV<float, R> jtrigf_bc_rows(RV<float, R> v) {
   double s4v, c3v;
   jtrig_coef_vgprs(s4v, c3v);
+  const uint32_t sm = jtrig_sign_sgpr();
   UNR for (int r = 0; r < R; ++r) {
-    v[r] = jtrigf_row_fast<KIND, CW>(v[r], s4v, c3v);
+    v[r] = jtrigf_row_fast<KIND, CW, QW_BC, ZFIX>(v[r], s4v, c3v, sm);
     if ((r + 1) % SRHIP_TRIG_ILP == 0) SRHIP_ROW_FENCE();
   }
   return v;
+}
+template <int R, int KIND, bool CW>
+__device__ __attribute__((noinline)) RV<float, R> jtrigf_bc(RV<float, R> v) {
+  if constexpr (KIND == 1 && SRHIP_TRIG_ZEROWAVE) {
+    // sin: the x == 0 rows once per wave -- a running min |x| (one instruction per row pair) and one
+    // compare, where the per-row form compares and selects in every row; a wave that holds a zero runs
+    // the same rows with the per-row form
+    const float mn = abs_fold<R, false>(1.0f, v);
+    if (__builtin_amdgcn_ballot_w64(mn == 0.0f) != 0) [[unlikely]] return jtrigf_bc_rows<R, KIND, CW, true>(v);
+    return jtrigf_bc_rows<R, KIND, CW, false>(v);
+  } else {
+    return jtrigf_bc_rows<R, KIND, CW, true>(v);
+  }
 }
 template <int R, int KIND>
 __device__ __attribute__((noinline)) RV<float, R> jtrigf_slow(RV<float, R> v) {
   double s4v, c3v;
   jtrig_coef_vgprs(s4v, c3v);
+  const uint32_t sm = jtrig_sign_sgpr();
   UNR for (int r = 0; r < R; ++r) {
     const float x = v[r];
-    v[r] = __builtin_fabsf(x) < SRM_PIO2F_BIG_F ? jtrigf_row_fast<KIND, true>(x, s4v, c3v) : srm_jtrigf(KIND, x);
+    v[r] = __builtin_fabsf(x) < SRM_PIO2F_BIG_F ? jtrigf_row_fast<KIND, true, QW_SLOW>(x, s4v, c3v, sm) : srm_jtrigf(KIND, x);
   }
   return v;
 }
@@ -572,7 +638,14 @@ __device__ __attribute__((always_inline)) inline RV<float, R> jtrigf_rows(const 
   const float mx = abs_fold<R, true>(0.0f, A);  // NaN-propagating: a NaN row fails every test below
   if (__builtin_amdgcn_ballot_w64(!(mx < SRM_JPIO4F)) == 0) return jtrigf_a<R, KIND>(v);
   if (__builtin_amdgcn_ballot_w64(!(mx <= SRM_J9PIO4F)) == 0) return jtrigf_bc<R, KIND, false>(v);
-  if (__builtin_amdgcn_ballot_w64(!(mx < SRM_PIO2F_BIG_F)) == 0) return jtrigf_bc<R, KIND, true>(v);
+  // tier C ends where its quadrant word is exact (|fn| < 2^20); a wave above it takes the slow body, whose
+  // fast rows carry the wide word (0.5 % of C2's live tier-C slots lie in such tiles)
+#if SRHIP_JTRIG_FAST && SRHIP_TRIG_QWORD
+  constexpr float c_end = SRM_JQW_MAXF;
+#else
+  constexpr float c_end = SRM_PIO2F_BIG_F;
+#endif
+  if (__builtin_amdgcn_ballot_w64(!(mx < c_end)) == 0) return jtrigf_bc<R, KIND, true>(v);
   return jtrigf_slow<R, KIND>(v);
 }
 
