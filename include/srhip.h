@@ -243,6 +243,14 @@ int srhip_eval_loss_expr(srhip_ctx* ctx, const srhip_dataset* ds, const srhip_pr
                          double* out_loss, uint8_t* out_ok);
 /* Rows of one block of the loss pass's summation (a compile-time constant of the library). */
 int32_t srhip_lossx_block_rows(void);
+/* The compiled program of a loss expression in execution order, for tests.  No device is needed.  *count
+ * receives the number of instructions, *need (may be NULL) the value slots the program uses; each of op, dst,
+ * a, b, imm (any may be NULL) the first min(count, cap) instructions' fields: op is an operator's device code
+ * (srhip_operators) or 0x100 + 0 / 1 / 2 / 3 for a load of the prediction / the target / the weight / a
+ * constant; dst the slot written; a and b the slots read (b of a unary operator and a, b of a load are 0); imm
+ * a constant load's bits in the expression's type (Float32 in the low word).  The result is in slot 0. */
+int srhip_loss_expr_instructions(const srhip_loss_expr* e, uint32_t* op, int32_t* dst, int32_t* a, int32_t* b,
+                                 uint64_t* imm, int32_t cap, int32_t* count, int32_t* need);
 /* srhip_eval_loss_expr in ONE launch: the interpreter's prediction mode with the loss program
  * behind it in the same kernel, the predictions in a scratch bounded by the launch geometry
  * (srhip_plan_eval_lossx), never ntrees * m.  out_loss / out_ok have exactly the bits of srhip_eval_loss_expr

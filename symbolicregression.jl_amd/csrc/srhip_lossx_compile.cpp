@@ -252,4 +252,21 @@ int srhip_loss_expr_eval_host(const srhip_loss_expr* e, const void* pred, const 
 
 int32_t srhip_lossx_block_rows(void) { return LOSSX_BLOCK_ROWS; }
 
+int srhip_loss_expr_instructions(const srhip_loss_expr* e, uint32_t* op, int32_t* dst, int32_t* a, int32_t* b, uint64_t* imm,
+                                 int32_t cap, int32_t* count, int32_t* need) {
+  if (!e || !count) return fail(SRHIP_ERR_INVALID, "loss expression instructions: null expression or count");
+  if (cap < 0) return fail(SRHIP_ERR_INVALID, "loss expression instructions: cap < 0");
+  *count = e->prog.n;
+  if (need) *need = e->prog.need;
+  for (int32_t i = 0; i < std::min(cap, e->prog.n); ++i) {
+    const LossxIns& I = e->prog.ins[i];
+    if (op) op[i] = I.op;
+    if (dst) dst[i] = I.dst;
+    if (a) a[i] = I.a;
+    if (b) b[i] = I.b;
+    if (imm) imm[i] = I.imm;
+  }
+  return SRHIP_OK;
+}
+
 }  // extern "C"

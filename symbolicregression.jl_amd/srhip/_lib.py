@@ -133,6 +133,8 @@ SIGNATURES = {
     "srhip_loss_expr_eval_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "srhip_eval_loss_expr": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "srhip_lossx_block_rows": (_i32, []),
+    "srhip_loss_expr_instructions": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.POINTER(_i32),
+                                                    ctypes.POINTER(_i32)]),
     "srhip_eval_loss_expr_fused": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "srhip_eval_loss_expr_submit": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_vp)]),
     "srhip_plan_eval_lossx": (ctypes.c_int, [ctypes.POINTER(LossxPlanQuery), ctypes.POINTER(LossxPlanInfo)]),

@@ -66,6 +66,21 @@ class ExprLoss:
         check(_lib.load().srhip_loss_expr_eval_host(self.handle(dt), ptr(p), ptr(yv), ptr(wv), p.size, ptr(out)))
         return out.reshape(shape) if shape else out[0]
 
+    def instructions(self, dtype):
+        """srhip_loss_expr_instructions: (ins, need) of the program compiled for dtype; ins is a list of
+        (op, dst, a, b, imm) in execution order, op an operator's device code or 0x100 .. 0x103 for a load of
+        the prediction, the target, the weight or a constant (imm: its bits in dtype)."""
+        lib = _lib.load()
+        h = self.handle(dtype)
+        n, need = ctypes.c_int32(), ctypes.c_int32()
+        check(lib.srhip_loss_expr_instructions(h, None, None, None, None, None, 0, ctypes.byref(n), ctypes.byref(need)))
+        op = np.zeros(n.value, dtype=np.uint32)
+        dst, a, b = (np.zeros(n.value, dtype=np.int32) for _ in range(3))
+        imm = np.zeros(n.value, dtype=np.uint64)
+        check(lib.srhip_loss_expr_instructions(h, ptr(op), ptr(dst), ptr(a), ptr(b), ptr(imm), n.value, ctypes.byref(n),
+                                               ctypes.byref(need)))
+        return [tuple(int(v[i]) for v in (op, dst, a, b, imm)) for i in range(n.value)], int(need.value)
+
     def close(self):
         for h in self._handles.values():
             _lib.load().srhip_loss_expr_destroy(h)
